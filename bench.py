@@ -24,6 +24,20 @@ normalize decision and rescale (a no-op unless the peak exceeds 1 or
   --config 5  config 4 + --normalize (per-file peaks; --peak-scope global adds
               the RCCL MAX all-reduce of the north-star variant)
 
+A plain run does only what `value` needs: set up, pre-roll and warm up, time
+the steps, write --dump-outputs, print the line.  --full adds everything else
+the line can carry, each a run of its own: the filter's exclusive launch time
+and the roofline figures built on it (with the PMC sidecar), the parity probe
+against the long-double oracle, the PCIe ingest probe and cpu_baseline
+(--no-parity / --no-ingest / --no-cpu-baseline and --kernel-launches then apply).
+
+--dump-outputs DIR writes what the last timed step left, as float32 .npy files:
+y_file<F>_<start>_<end>.npy per shard of this rank ([channels][end - start], or,
+beyond the size budget, its values at a fixed seeded set of flat positions:
+dump_positions) and peaks.npy (peaks_rank<R>.npy with more than one rank), the
+per-file peak vector.  The inputs are seeded (synth.py), so two builds run with
+the same arguments can be compared file for file.
+
 Prints ONE JSON line on rank 0.
 """
 from __future__ import annotations
@@ -53,6 +67,12 @@ def parse():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--config", type=int, default=2, choices=[1, 2, 3, 4, 5])
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what `value` does not need: the exclusive kernel time and its "
+                         "roofline figures, the parity probe, the ingest probe, cpu_baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last step's outputs to DIR as float32 .npy "
+                         "(whole, or a fixed seeded sample beyond the size budget)")
     ap.add_argument("--method", default="auto", choices=["auto", "direct", "fft"])
     ap.add_argument("--files", type=int, default=None, help="files in the batch (configs 4/5)")
     ap.add_argument("--seconds", type=float, default=None, help="file length in seconds")
@@ -83,13 +103,13 @@ def parse():
                          "launches (CHANGELOG.md s5), and a 20-step timed region would otherwise "
                          "sit in that ramp.  0 = off")
     ap.add_argument("--kernel-launches", type=int, default=20,
-                    help="launches of the filter alone, one stream, right after the pre-roll: "
+                    help="--full: launches of the filter alone, one stream, right after the pre-roll: "
                          "the exclusive kernel time roofline.kernel_ms is measured on")
     ap.add_argument("--force-exchange", action="store_true",
                     help="run the peak all-reduce every step even where the plan needs none (at --gpus 1: "
                          "a world-1 RCCL group; config 5 --files 1 is then the N = 8 per-rank step)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without cpu_baseline")
+    ap.add_argument("--no-parity", action="store_true", help="--full without the parity probe")
     ap.add_argument("--graph", choices=["auto", "on", "off"], default="auto",
                     help="replay the steps from a captured HIP graph (batch.GraphedSteps: 2 x lanes "
                          "steps per replay); auto = on for config 1, whose 48 000-sample steps are "
@@ -428,6 +448,50 @@ def preroll(step, seconds, sync, agree=None, batch=8):
     return steps
 
 
+DUMP_BUDGET_BYTES = 60_000_000  # all files of one --dump-outputs, every rank's together (< 64 MB)
+DUMP_EDGE = 4096                # flat positions kept at both ends of a sampled shard
+
+
+def dump_positions(file, start, numel, k):
+    """The flat positions of a [channels][count] shard output that a sampled
+    dump keeps: the first and last DUMP_EDGE and up to k drawn by a generator
+    seeded with (file, start), sorted, duplicates dropped.  A pure function of
+    its arguments, so two runs sample the same positions."""
+    import numpy as np
+    edge = min(DUMP_EDGE, numel)
+    rng = np.random.default_rng([20260206, file, start])
+    return np.unique(np.r_[np.arange(edge), np.arange(numel - edge, numel),
+                           rng.integers(0, numel, max(0, k - 2 * edge))])
+
+
+def dump_outputs(out_dir, results, peaks, rank, world, torch):
+    """Write the latest step's outputs (BatchRunner.results() and its peak
+    vector) under out_dir as float32 .npy; returns the manifest for the result
+    line.  Every rank writes its own shards within budget / world bytes."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    pk = peaks.detach().to("cpu", torch.float32).numpy()
+    budget = (DUMP_BUDGET_BYTES // world - pk.nbytes - 128 * (len(results) + 1)) // 4  # in f32 values
+    total = sum(y.numel() for _, y in results)
+    files = {}
+
+    def save(name, a):
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        files[name] = {"shape": list(a.shape), "dtype": str(a.dtype)}
+
+    for sh, y in results:
+        name = f"y_file{sh.file}_{sh.start}_{sh.end}"
+        if total <= budget:
+            save(name, y.detach().to("cpu", torch.float32).numpy())
+        else:
+            idx = dump_positions(sh.file, sh.start, y.numel(), budget * y.numel() // total)
+            got = y.detach().reshape(-1).index_select(0, torch.from_numpy(idx).to(y.device))
+            save(name, got.to("cpu", torch.float32).numpy())
+            files[name]["sample_of"] = list(y.shape)
+    save("peaks" if world == 1 else f"peaks_rank{rank}", pk)
+    return {"dir": out_dir, "rank": rank, "files": files,
+            "bytes": sum(os.path.getsize(os.path.join(out_dir, n + ".npy")) for n in files)}
+
 
 KERNEL_NAMES = {"l16": "fir_fft_f64_kernel", "l32_park": "fir_fft32_f64_kernel", "l32_reg": "fir_fft32r_kernel"}
 
@@ -551,10 +615,11 @@ def main():
     # long: the clock falls as soon as the GPU idles).  Under two lanes the
     # timed steps' launches overlap by a tail round, so their start-to-end
     # events (overlapped_ms) are not one launch's duration.
+    # --full only: a plain run's line carries no exclusive kernel time.
     backend.set_lane(0)
     backend.events = []
     peaks_scratch = backend.new_peaks(len(runner.nframes))
-    for i in range(2 * args.kernel_launches):
+    for i in range(2 * args.kernel_launches if args.full else 0):
         backend.record = i >= args.kernel_launches  # the first half: untimed lead-in
         sh = runner.shards[i % len(runner.shards)] if runner.shards else None
         if sh is None:
@@ -566,7 +631,7 @@ def main():
     torch.cuda.synchronize(dev)
     backend.record = False
     kern_launches = len(backend.events)
-    kern_ms = sum(a.elapsed_time(b) for a, b in backend.events) / max(1, kern_launches)
+    kern_ms = sum(a.elapsed_time(b) for a, b in backend.events) / kern_launches if kern_launches else None
     backend.events = []
     for _ in range(args.warmup):
         runner.step()
@@ -598,21 +663,28 @@ def main():
     launches = len(backend.events)
     overlapped_ms = sum(a.elapsed_time(b) for a, b in backend.events) / max(1, launches)
     samples_per_launch = my_samples / max(1, len(runner.shards))
-    # parity of the LAST timed step's outputs (rank 0's first shard), copied
-    # out before anything else runs on the device
+    # the LAST timed step's outputs, read before anything else runs on the
+    # device: --dump-outputs (every rank), and under --full the parity probe's
+    # copy (rank 0's first shard)
+    want_probe = args.full and rank == 0 and not args.no_parity and bool(runner.shards)
+    results = runner.results() if args.dump_outputs or want_probe else []
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, results, runner.peaks, rank, world, torch)
     probe = None
-    if rank == 0 and not args.no_parity and runner.shards:
-        sh0, y0 = runner.results()[0]
+    if want_probe:
+        sh0, y0 = results[0]
         probe = (sh0, y0.cpu().numpy(), float(runner.peaks[sh0.file].item()))
 
     ingest = None
-    if not args.no_ingest and runner.shards:
+    if args.full and not args.no_ingest and runner.shards:
         ingest = ingest_probe(torch, lcfir, file_samples(runner.shards[0].file), bits, dev)
 
     props = torch.cuda.get_device_properties(dev)
     mine = {"rank": rank, "device": f"{props.pci_domain_id:04x}:{props.pci_bus_id:02x}:{props.pci_device_id:02x}"
                                     f" (cuda:{local})",
-            "ms_per_step": round(elapsed / args.steps * 1e3, 4), "kernel_ms": round(kern_ms, 6),
+            "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+            "kernel_ms": round(kern_ms, 6) if kern_ms is not None else None,
             "allreduce_ms_per_step": (round(collective.mean_ms(), 4) if collective.events else None),
             "samples": my_samples}
     records = [mine]
@@ -621,23 +693,34 @@ def main():
         dist.all_gather_object(records, mine)
     total_samples = torch.tensor([float(my_samples)], dtype=torch.float64, device=dev)
     if world > 1:
-        t = torch.tensor([elapsed, kern_ms], dtype=torch.float64, device=dev)
+        t = torch.tensor([elapsed, kern_ms or 0.0], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed, kern_ms = float(t[0]), float(t[1])
+        elapsed, kern_ms = float(t[0]), float(t[1]) or None
         dist.all_reduce(total_samples, op=dist.ReduceOp.SUM)
     total = float(total_samples[0]) * args.steps
     value = total / elapsed / 1e6
-    kern_s = kern_ms / 1e3
-    achieved = 4.0 * samples_per_launch / kern_s / 1e9
     ms_per_step = elapsed / args.steps * 1e3
     # the whole step against the same roofline: per GPU, 4 B x samples per
     # step / ms_per_step (includes launch gaps, the collective and any
     # normalize pass; with lanes > 1 consecutive steps overlap)
     achieved_step = 4.0 * total / world / elapsed / 1e9
     launches_per_step = max(1, len(runner.shards))
-    direct_tflops = 2.0 * args.ntaps * samples_per_launch / kern_s / 1e12
 
     if rank == 0:
+        kname = fft_kernel_name(flt.fft_units) if method == "fft" else "fir_direct_f64_kernel"
+        # a plain run: the whole step against the HBM roofline, from ms_per_step alone
+        roofline = {
+            "bound": "hbm",
+            "achieved": round(achieved_step, 3),
+            "peak": HBM_PEAK_GBPS,
+            "unit": "GB/s",
+            "frac": round(achieved_step / HBM_PEAK_GBPS, 6),
+            "basis": "whole step: 4 B x samples per step per GPU / ms_per_step (launch gaps, collective, "
+                     "normalize passes, lane overlap included); --full measures the filter's exclusive "
+                     "launch time and reports achieved / frac on it, this figure as frac_step",
+            "kernel": kname,
+            "bytes_per_unit": 4,
+        }
         rms, npos, worst_ulp = None, 0, None
         if probe is not None:
             sh0, y0, peak0 = probe
@@ -646,67 +729,34 @@ def main():
             if args.normalize or peak0 > 1.0:
                 gain = 1.0 / float(np.float32(peak0))  # the pass's f64 factor (peak_scale.hpp)
             rms, npos, worst_ulp = parity_probe(x, y0, taps, sh0.start, gain)
-        # the PMC sidecar of this exact launch shape AND this library build
-        # (--traffic-json, else any profiles/traffic_*.json; select_sidecar)
-        plan = flt.fft_info if method == "fft" else {}
-        kname = fft_kernel_name(flt.fft_units) if method == "fft" else "fir_direct_f64_kernel"
-        sidecars = [args.traffic_json] + sorted(glob.glob(os.path.join(ROOT, "profiles", "traffic_*.json")))
-        tj, traffic_source = select_sidecar(sidecars, lcfir.build_id(), method, args.ntaps, samples_per_launch,
-                                            plan.get("seg_len"), kname)
-        traffic = tj.get("hbm_bytes_per_launch") if tj else None
-        f64_flops = tj.get("f64_flops_per_launch") if tj else None
-        valu_insts = tj.get("valu_insts_per_launch") if tj else None
-        # The f64 kernels are bound by VALU issue, not HBM: the launch's PMC
-        # instruction counts (profiles/traffic_latest.json) over the live kernel time.
-        # The resource whose floor is higher for this launch.  The direct form
-        # issues one fma per tap rounded up to 16 (fir_direct.hpp) against 8 B
-        # of HBM read + write per sample: below ~40 taps HBM is the floor.  The
-        # FFT is bound by its f64 issue and LDS-exchange latency (DESIGN s4.2).
-        if method == "direct":
-            t16 = (args.ntaps + 15) // 16 * 16
-            binding = "hbm" if 8.0 / (HBM_PEAK_GBPS * 1e9) > 2.0 * t16 / (FP64_PEAK_TFLOPS * 1e12) else "fp64-valu"
-        else:
-            binding = "fp64-valu"
-        simds = 4 * torch.cuda.get_device_properties(dev).multi_processor_count
-        fp64_tflops = f64_flops / kern_s / 1e12 if f64_flops else None
-        valu_frac = valu_insts * VALU_NS_PER_INST * 1e-9 / (simds * kern_s) if valu_insts else None
-        wl = {1: "config1: 1 s mono 48 kHz int16 file per GPU (-f 20 -s 10)",
-              2: "config2: 10 min stereo 48 kHz int24 file per GPU",
-              3: f"config3: {args.seconds:g} s 8-channel 96 kHz float32 file per GPU",
-              4: f"config4: {nfiles} x {args.seconds / 60:g} min stereo 48 kHz int24 files",
-              5: f"config5: {nfiles} x {args.seconds / 60:g} min stereo 48 kHz int24 files, "
-                 f"--normalize"}
-        line = {
-            "metric": METRIC,
-            "value": round(value, 3),
-            "unit": "Msamples/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 4),
-            "higher_is_better": True,
-            "scaling": "weak" if per_gpu else "strong",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": f"synthetic (SURVEY.md s8d {'int%d' % bits if bits else 'float32'} generator), "
-                    f"resident in HBM",
-            "config": {
-                "workload": wl[args.config] + f", {args.ntaps}-tap low-cut",
-                "files": nfiles, "channels": nch, "samples_per_channel": n,
-                "ntaps": args.ntaps, "method": method,
-                "fft_plan": dict(flt.fft_info, kernel=fft_kernel_name(flt.fft_units)) if method == "fft" else None,
-                "parallelism": f"{world} rank(s), files sharded by batch.plan_shards",
-                "normalize": bool(args.normalize), "peak_scope": args.peak_scope,
-                "peak_exchange": runner.exchange,
-                "fused_normalize": runner.fuse and len(runner.shards) > 1,
-                # whole run (pre-roll included): normalizes carried inside a
-                # filter launch vs run as their own pass (lcfir_ctx_nrm_stats)
-                "normalize_launches": flt.nrm_stats if args.normalize else None,
-                "lanes": args.lanes,
-                "hip_graph": {"replays": n_replay, "steps_per_replay": graphed.per_replay,
-                              "graphs": len(graphed.graphs), "eager_steps": n_eager} if graphed else None,
-            },
-            "roofline": {
+        if args.full and kern_ms:
+            kern_s = kern_ms / 1e3
+            achieved = 4.0 * samples_per_launch / kern_s / 1e9
+            direct_tflops = 2.0 * args.ntaps * samples_per_launch / kern_s / 1e12
+            # the PMC sidecar of this exact launch shape AND this library build
+            # (--traffic-json, else any profiles/traffic_*.json; select_sidecar)
+            plan = flt.fft_info if method == "fft" else {}
+            sidecars = [args.traffic_json] + sorted(glob.glob(os.path.join(ROOT, "profiles", "traffic_*.json")))
+            tj, traffic_source = select_sidecar(sidecars, lcfir.build_id(), method, args.ntaps, samples_per_launch,
+                                                plan.get("seg_len"), kname)
+            traffic = tj.get("hbm_bytes_per_launch") if tj else None
+            f64_flops = tj.get("f64_flops_per_launch") if tj else None
+            valu_insts = tj.get("valu_insts_per_launch") if tj else None
+            # The f64 kernels are bound by VALU issue, not HBM: the launch's PMC
+            # instruction counts (profiles/traffic_latest.json) over the live kernel time.
+            # The resource whose floor is higher for this launch.  The direct form
+            # issues one fma per tap rounded up to 16 (fir_direct.hpp) against 8 B
+            # of HBM read + write per sample: below ~40 taps HBM is the floor.  The
+            # FFT is bound by its f64 issue and LDS-exchange latency (DESIGN s4.2).
+            if method == "direct":
+                t16 = (args.ntaps + 15) // 16 * 16
+                binding = "hbm" if 8.0 / (HBM_PEAK_GBPS * 1e9) > 2.0 * t16 / (FP64_PEAK_TFLOPS * 1e12) else "fp64-valu"
+            else:
+                binding = "fp64-valu"
+            simds = 4 * torch.cuda.get_device_properties(dev).multi_processor_count
+            fp64_tflops = f64_flops / kern_s / 1e12 if f64_flops else None
+            valu_frac = valu_insts * VALU_NS_PER_INST * 1e-9 / (simds * kern_s) if valu_insts else None
+            roofline = {
                 "bound": "hbm",
                 "achieved": round(achieved, 3),
                 "peak": HBM_PEAK_GBPS,
@@ -746,7 +796,44 @@ def main():
                 "valu_issue_note": "PMC VALU wave-instructions per launch x 1.71 ns / (SIMDs x kernel time); "
                                    "1.71 ns = the f64 pipe's measured ceiling for the kernel's own "
                                    "instruction mix (tools/valu_mix.hip, max clock)",
+            }
+        wl = {1: "config1: 1 s mono 48 kHz int16 file per GPU (-f 20 -s 10)",
+              2: "config2: 10 min stereo 48 kHz int24 file per GPU",
+              3: f"config3: {args.seconds:g} s 8-channel 96 kHz float32 file per GPU",
+              4: f"config4: {nfiles} x {args.seconds / 60:g} min stereo 48 kHz int24 files",
+              5: f"config5: {nfiles} x {args.seconds / 60:g} min stereo 48 kHz int24 files, "
+                 f"--normalize"}
+        line = {
+            "metric": METRIC,
+            "value": round(value, 3),
+            "unit": "Msamples/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(ms_per_step, 4),
+            "higher_is_better": True,
+            "scaling": "weak" if per_gpu else "strong",
+            "vs_baseline": None,
+            "dtype": "f64",
+            "data": f"synthetic (SURVEY.md s8d {'int%d' % bits if bits else 'float32'} generator), "
+                    f"resident in HBM",
+            "config": {
+                "workload": wl[args.config] + f", {args.ntaps}-tap low-cut",
+                "files": nfiles, "channels": nch, "samples_per_channel": n,
+                "ntaps": args.ntaps, "method": method,
+                "fft_plan": dict(flt.fft_info, kernel=fft_kernel_name(flt.fft_units)) if method == "fft" else None,
+                "parallelism": f"{world} rank(s), files sharded by batch.plan_shards",
+                "normalize": bool(args.normalize), "peak_scope": args.peak_scope,
+                "peak_exchange": runner.exchange,
+                "fused_normalize": runner.fuse and len(runner.shards) > 1,
+                # whole run (pre-roll included): normalizes carried inside a
+                # filter launch vs run as their own pass (lcfir_ctx_nrm_stats)
+                "normalize_launches": flt.nrm_stats if args.normalize else None,
+                "lanes": args.lanes,
+                "hip_graph": {"replays": n_replay, "steps_per_replay": graphed.per_replay,
+                              "graphs": len(graphed.graphs), "eager_steps": n_eager} if graphed else None,
             },
+            "roofline": roofline,
             "parity": {"rms_vs_longdouble": rms, "max_ulp": worst_ulp, "positions": npos,
                        "tol": 1e-9, "of": "outputs of the last timed step (rank 0, first shard)"},
             "preroll": {"seconds": round(preroll_s, 3), "steps": preroll_steps},
@@ -754,9 +841,14 @@ def main():
             # all-reduce time is the peak exchange's HIP-event span per step
             "ranks": rank_spread(records),
         }
+        line["full"] = args.full
+        if not args.full:
+            del line["parity"]  # no probe ran
+        if dumped is not None:
+            line["outputs"] = dumped  # rank 0's files
         if ingest is not None:
             line["ingest"] = ingest  # rank 0's
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(file_samples(0).reshape(-1), taps,
                                                 args.cpu_seconds, single_thread=args.config == 1)
         print(json.dumps(line), flush=True)

@@ -7,7 +7,7 @@
 # usage (repo root, on the GPU box): bash scripts/gpu_run.sh TAG STEP [STEP ...]
 #   smoke                   __graft_entry__.smoke()
 #   suite[:ARGS]            pytest -m gpu over tests/ (ARGS: the files / pytest args instead)
-#   bench[:ARGS]            bench.py --steps 20 --warmup 5 ARGS (the driver's shape)
+#   bench[:ARGS]            bench.py --full --steps 20 --warmup 5 ARGS (the driver's shape, every probe)
 #   ab:V1,V2:REPS[:ARGS]    alternating bench lines of abvar/V1.so, abvar/V2.so, ...
 #                           (scripts/build_variant.sh builds them; "prod" = this tree's library)
 #   parity:V[:ARGS]         the FFT parity + fuzz tests with abvar/V.so in place
@@ -84,14 +84,14 @@ for S in "$@"; do
     case $kind in
     smoke) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
     suite) run suite 1500 python -u -m pytest ${rest:-tests} -m gpu -x -v --timeout 300 --timeout-method thread ;;
-    bench) run bench 400 python bench.py --steps 20 --warmup 5 $rest ;;
+    bench) run bench 400 python bench.py --full --steps 20 --warmup 5 $rest ;;
     ab)
         vs=${rest%%:*}; r2=${rest#*:}; reps=${r2%%:*}; args=""; [ "$r2" != "$reps" ] && args=${r2#*:}
         for rep in $(seq 1 "$reps"); do
             for v in ${vs//,/ }; do
                 if [ "$v" = prod ]; then restore; else cp "abvar/$v.so" "$LIB"; fi
                 N=$((N + 1)); log="$OUT/${N}_ab_${v}_$rep.log"
-                timeout -k 10 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-ingest $args > "$log" 2>&1 \
+                timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-ingest $args > "$log" 2>&1 \
                     || { echo "!! ab $v failed"; tail -20 "$log"; exit 1; }
                 echo "$v rep$rep $(brief < "$log") [$args]" | tee -a "$OUT/ab.txt"
             done
@@ -117,7 +117,7 @@ for S in "$@"; do
         d="$OUT/prof$((N + 1))"
         cd /tmp; export TMPDIR=/tmp
         run prof 600 rocprofv3 --kernel-trace --stats -f csv -d "$d" -o bench -- \
-            python3 "$ROOT/bench.py" --steps 20 --warmup 5 --no-cpu-baseline --no-parity --no-ingest $rest
+            python3 "$ROOT/bench.py" --full --steps 20 --warmup 5 --no-cpu-baseline --no-parity --no-ingest $rest
         cd "$ROOT"
         python3 scripts/trace_exclusive.py "$d/bench_kernel_trace.csv" > "$d/exclusive_from_trace.json"
         head -c 600 "$d/exclusive_from_trace.json"; echo ;;
@@ -132,7 +132,7 @@ for S in "$@"; do
         for c in "${passes[@]}"; do
             i=$((i + 1))
             run "${kind}_$i" 300 rocprofv3 --pmc $c --kernel-include-regex "$re" -f csv \
-                -d "$d/p_$i" -o pmc -- python3 "$ROOT/bench.py" --steps 3 --warmup 1 --no-cpu-baseline \
+                -d "$d/p_$i" -o pmc -- python3 "$ROOT/bench.py" --full --steps 3 --warmup 1 --no-cpu-baseline \
                 --no-parity --no-ingest $rest
         done
         cd "$ROOT"
@@ -144,7 +144,7 @@ for S in "$@"; do
         d="$OUT/pmcx$((N + 1))"
         cd /tmp; export TMPDIR=/tmp
         run pmcx 300 rocprofv3 --pmc ${cl//,/ } --kernel-include-regex "$re" -f csv -d "$d/p_1" -o pmc -- \
-            python3 "$ROOT/bench.py" --steps 3 --warmup 1 --no-cpu-baseline --no-parity --no-ingest ${targs:-}
+            python3 "$ROOT/bench.py" --full --steps 3 --warmup 1 --no-cpu-baseline --no-parity --no-ingest ${targs:-}
         cd "$ROOT"
         python3 scripts/pmc_summary.py "$d" --json "$d/pmc_summary.json" > /dev/null && cat "$d/pmc_summary.json" ;;
     traffic) # traffic:NTAPS:SAMPLES_PER_LAUNCH:KERNEL:SEG_LEN[:ARGS] -- the bench's PMC sidecar
@@ -156,7 +156,7 @@ for S in "$@"; do
         for c in FETCH_SIZE WRITE_SIZE "SQ_INSTS_VALU SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_FMA_F64"; do
             i=$((i + 1))
             run "traffic_$i" 300 rocprofv3 --pmc $c --kernel-include-regex "$kern" -f csv -d "$d/p_$i" -o pmc -- \
-                python3 "$ROOT/bench.py" --steps 3 --warmup 1 --no-cpu-baseline --no-parity --no-ingest --ntaps "$nt" ${targs:-}
+                python3 "$ROOT/bench.py" --full --steps 3 --warmup 1 --no-cpu-baseline --no-parity --no-ingest --ntaps "$nt" ${targs:-}
         done
         cd "$ROOT"
         python3 scripts/pmc_summary.py "$d" --json "$d/pmc_summary.json" > /dev/null &&
@@ -182,7 +182,7 @@ for S in "$@"; do
             "$ROOT/tests/cpp/dropin_bench" ${args:---threads 16 --reps 1 --modes pinned}
         cd "$ROOT"; restore
         python3 scripts/copy_overlap.py "$d" | tee "$d/overlap.txt" ;;
-    gpus2) LCFIR_BENCH_SHARE_DEVICE=1 run gpus2 400 python bench.py --gpus 2 --steps 10 --warmup 2 $rest ;;
+    gpus2) LCFIR_BENCH_SHARE_DEVICE=1 run gpus2 400 python bench.py --full --gpus 2 --steps 10 --warmup 2 $rest ;;
     *) echo "unknown step $S"; exit 2 ;;
     esac
 done

@@ -1,7 +1,7 @@
 """Average duration of bench.py's exclusive filter launches, read from a
 rocprofv3 --kernel-trace csv of the bench command itself.
 
-bench.py times roofline.kernel_ms on 2 x --kernel-launches back-to-back
+bench.py --full times roofline.kernel_ms on 2 x --kernel-launches back-to-back
 filter launches on one stream right after the pre-roll (the first half an
 untimed lead-in).  In the trace they are the only long run of consecutive,
 non-overlapping launches on one queue (the pre-roll and timed steps

@@ -68,6 +68,11 @@ def test_bare_gpus2_starts_two_ranks_and_propagates_failure():
     env.pop("WORLD_SIZE", None)
     env.pop("LCFIR_BENCH_SHARE_DEVICE", None)
     env["HIP_VISIBLE_DEVICES"] = ""
+    # the launcher ends the other rank as soon as it sees one fail, and it looks
+    # every 0.1 s by default: on a loaded host the slower rank then dies before
+    # its own check.  Looking every 4 s (torch.distributed.run reads its options'
+    # defaults from PET_*) lets both ranks get there.
+    env["PET_MONITOR_INTERVAL"] = "4"
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1"],
                          cwd=ROOT, capture_output=True, text=True, timeout=170, env=env)
     assert out.returncode != 0
@@ -112,6 +117,52 @@ def test_rank_spread_reduction():
     recs = [dict(d, allreduce_ms_per_step=None) for d in recs]
     r = bench.rank_spread(recs)
     assert r["allreduce_ms_per_step"] == [None, None] and r["allreduce_ms_per_step_max"] is None
+
+
+def test_dump_positions_fixed_and_bounded():
+    """--dump-outputs' sample of a large shard: the same positions on every
+    call, both edges kept, sorted, at most k of them, all in range."""
+    import numpy as np
+    a = bench.dump_positions(3, 1000, 10_000_000, 50_000)
+    b = bench.dump_positions(3, 1000, 10_000_000, 50_000)
+    assert np.array_equal(a, b) and a.size <= 50_000 and a.size > 40_000
+    assert np.all(np.diff(a) > 0) and a[0] == 0 and a[-1] == 10_000_000 - 1
+    assert np.array_equal(a[:bench.DUMP_EDGE], np.arange(bench.DUMP_EDGE))
+    assert not np.array_equal(a, bench.dump_positions(4, 1000, 10_000_000, 50_000))
+    tiny = bench.dump_positions(0, 0, 100, 10_000)  # fewer values than the edges: every position once
+    assert np.array_equal(tiny, np.arange(100))
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """dump_outputs writes every shard and the peaks as float32 .npy: whole
+    within the budget, the dump_positions sample beyond it, never more bytes
+    than the budget."""
+    import numpy as np
+    import torch
+    import batch
+    ys = [torch.arange(2 * 5000, dtype=torch.float32).reshape(2, 5000) * 0.5,
+          torch.arange(2 * 3000, dtype=torch.float32).reshape(2, 3000) - 7.0]
+    results = [(batch.Shard(0, 0, 5000), ys[0]), (batch.Shard(1, 100, 3100), ys[1])]
+    peaks = torch.tensor([2.5, 1.25])
+    whole = bench.dump_outputs(str(tmp_path / "whole"), results, peaks, 0, 1, torch)
+    assert set(whole["files"]) == {"y_file0_0_5000", "y_file1_100_3100", "peaks"}
+    for (sh, y), name in zip(results, ("y_file0_0_5000", "y_file1_100_3100")):
+        got = np.load(tmp_path / "whole" / f"{name}.npy")
+        assert got.dtype == np.float32 and np.array_equal(got, y.numpy())
+    assert np.array_equal(np.load(tmp_path / "whole" / "peaks.npy"), np.float32([2.5, 1.25]))
+
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 2 * 20_000)  # per rank of 2: 5 000 values, 16 000 exist
+    monkeypatch.setattr(bench, "DUMP_EDGE", 64)
+    part = bench.dump_outputs(str(tmp_path / "part"), results, peaks, 1, 2, torch)
+    assert set(part["files"]) == {"y_file0_0_5000", "y_file1_100_3100", "peaks_rank1"}
+    assert part["bytes"] <= 20_000
+    for (sh, y), name in zip(results, ("y_file0_0_5000", "y_file1_100_3100")):
+        got = np.load(tmp_path / "part" / f"{name}.npy")
+        k = (20_000 - 8 - 128 * 3) // 4 * y.numel() // 16_000
+        idx = bench.dump_positions(sh.file, sh.start, y.numel(), k)
+        assert got.dtype == np.float32 and got.ndim == 1 and 2 * 64 < got.size <= k
+        assert np.array_equal(got, y.numpy().reshape(-1)[idx])
+        assert part["files"][name]["sample_of"] == list(y.shape)
 
 
 def _gather_worker(rank, world):
