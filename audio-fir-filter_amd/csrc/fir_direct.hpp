@@ -10,8 +10,11 @@
 //   * a tile is BO = NT*R consecutive outputs of one channel; a workgroup
 //     walks its channel's tiles (the grid is capped, fir_direct_f64_kernel);
 //   * lane `tid` owns the R consecutive outputs n0 + tid*R + [0, R);
-//   * taps are processed in stages of <= TC taps (rounded up to R with zero
-//     taps): each stage converts the sample window x[n0 - half + c, +BO+kc)
+//   * taps are processed in stages of <= TC taps (the window rounded up to R;
+//     the last ntaps % R taps run a count-bounded block, fma_tail, so exactly
+//     the T real taps are multiplied and an output depends on
+//     x[n - half, n + half] alone, non-finite samples included): each stage
+//     converts the sample window x[n0 - half + c, +BO+kc)
 //     to f64 into LDS (once per staged sample, not per tap), then every lane
 //     slides a 2R-sample register window over its part of the LDS window: per
 //     R taps it reads R samples (ds_read_b64) and R wave-uniform taps (scalar
@@ -69,6 +72,33 @@ __device__ __forceinline__ void fma_block(double (&acc)[R], const double (&wlo)[
             acc[r] = __builtin_fma(h, w, acc[r]);
         }
     }
+}
+
+// The filter's last nu < R taps.  The count is wave-uniform (a scalar branch
+// per tap): the zero taps that round the device copy up to R are never
+// multiplied, so a sample past an output's support -- NaN or Inf times a zero
+// tap is NaN -- cannot reach it.
+template <int R, int U>
+__device__ __forceinline__ void fma_tail_from(double (&acc)[R], const double (&wlo)[R],
+                                              const double (&whi)[R], const double (&h)[R], int nu) {
+    if constexpr (U < R) {
+        if (U < nu) {
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const double w = (r + U < R) ? wlo[r + U] : whi[r + U - R];
+                acc[r] = __builtin_fma(h[U], w, acc[r]);
+            }
+            fma_tail_from<R, U + 1>(acc, wlo, whi, h, nu); // nested: the first u >= nu leaves
+        }
+    }
+}
+template <int R>
+__device__ __forceinline__ void fma_tail(double (&acc)[R], const double (&wlo)[R],
+                                         const double (&whi)[R], ctap_ptr t, int nu) {
+    double h[R]; // the whole block of the zero-padded copy in one batch of scalar loads, as fma_block's
+#pragma unroll
+    for (int u = 0; u < R; ++u) h[u] = t[u];
+    fma_tail_from<R, 0>(acc, wlo, whi, h, nu);
 }
 
 // The window of one stage: x[g0, g0 + win) of the channel into v, element
@@ -185,9 +215,13 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(kDirectWaves
             double wa[R], wb[R];
 #pragma unroll
             for (int j = 0; j < R; ++j) wa[j] = wp[j];
+            // whole R-tap blocks of the stage's real taps; the filter's last
+            // ntaps % R taps (last stage only) go through fma_tail
+            const int kreal = p.ntaps - c < TC ? p.ntaps - c : TC;
+            const int kfull = kreal / R * R;
             int k = 0;
 #pragma unroll 1
-            for (; k + 2 * R <= kc; k += 2 * R) {
+            for (; k + 2 * R <= kfull; k += 2 * R) {
                 const int blk = k / R; // window block index (R samples per block, R+1 with pad)
 #pragma unroll
                 for (int j = 0; j < R; ++j) wb[j] = wp[(blk + 1) * (R + 1) + j];
@@ -196,11 +230,21 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(kDirectWaves
                 for (int j = 0; j < R; ++j) wa[j] = wp[(blk + 2) * (R + 1) + j];
                 fma_block<R>(acc, wb, wa, taps + c + k + R);
             }
-            if (k < kc) { // an odd number of R-tap blocks: the last one
+            if (k < kfull) { // an odd number of whole blocks: the last one
                 const int blk = k / R;
 #pragma unroll
                 for (int j = 0; j < R; ++j) wb[j] = wp[(blk + 1) * (R + 1) + j];
                 fma_block<R>(acc, wa, wb, taps + c + k);
+                if (kfull < kreal) {
+#pragma unroll
+                    for (int j = 0; j < R; ++j) wa[j] = wp[(blk + 2) * (R + 1) + j];
+                    fma_tail<R>(acc, wb, wa, taps + c + kfull, kreal - kfull);
+                }
+            } else if (kfull < kreal) {
+                const int blk = k / R;
+#pragma unroll
+                for (int j = 0; j < R; ++j) wb[j] = wp[(blk + 1) * (R + 1) + j];
+                fma_tail<R>(acc, wa, wb, taps + c + kfull, kreal - kfull);
             }
             __syncthreads();
         }

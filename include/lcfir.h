@@ -22,6 +22,28 @@
  *     y[n] = (float) sum_{k=0}^{T-1} h[k] * x[n - M/2 + k],   x[i] = 0 outside [0, N)
  * with T = M + 1 odd taps (WindowedSinc kernel length, getMo2() = M/2),
  * f32 samples, f64 taps, f64 accumulation, one round-to-nearest-even to f32.
+ *
+ * The samples' value domain (a float source can hold any bit pattern;
+ * tests/test_gpu_value_domain.py):
+ *   - direct method: exact support.  y[n] depends on x[n - M/2, n + M/2]
+ *     alone, so one NaN or +-Inf sample makes exactly the T outputs whose taps
+ *     reach it non-finite, as the reference's fms() would (Inf times a zero
+ *     tap, and Inf - Inf, are NaN); every other output keeps its bits.
+ *   - FFT method: overlap-save mixes a segment's samples, so every output of
+ *     a segment whose input window (lcfir_ctx_window of the segment's outputs)
+ *     holds a non-finite sample becomes non-finite.  Nothing else changes:
+ *     the other segments, the other channels and their peaks, the buffer a
+ *     fused normalize rescales, and later calls on the same ctx keep their bits.
+ *   - Finite samples whose sum passes f32's range narrow to +-Inf.
+ *   - The peak is max |y| with NaN skipped and Inf taken (0 for a channel of
+ *     NaN).  A peak of Inf normalizes with gain 1 / Inf = 0: finite samples
+ *     become signed zeros, Inf and NaN become NaN, as `if (maxMag > 1.0f)
+ *     normalize()` (ProcessFile.cp:98-101) would with a scale of 1 / maxMag.
+ *   - Scale invariance: y(2^k x) = 2^k y(x) bit for bit, for every method,
+ *     wherever both sides are normal f32 (power-of-two scaling is exact in
+ *     f64 fma, mul and add); nothing has an absolute floor.
+ *   - Subnormal samples, outputs and peaks are honoured: nothing flushes to 0.
+ *   - The f32 codec formats move bits (NaN payloads survive decode and encode).
  */
 #ifndef LCFIR_H
 #define LCFIR_H

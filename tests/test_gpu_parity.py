@@ -3,7 +3,9 @@
 Bars (written here, used below):
   * METHOD direct: bit-exact against the oracle's strict-order f64 FMA chain
     (ORACLE_FMA) -- same accumulation order and rounding, so any difference is
-    a bug;
+    a bug (the inputs here are finite and near full scale; NaN, +-Inf,
+    subnormal and 2^k-scaled samples are held to the same oracle, and the FFT
+    forms to their containment contract, in test_gpu_value_domain.py);
   * every method: RMS(y_gpu - y_longdouble) <= 1e-9 in full-scale units
     (BASELINE.json north_star), and at most 1 ulp(f32) per sample (samples
     within 1e-12 of the reference are exempt from the ulp count).
