@@ -216,7 +216,7 @@ constexpr double kFft32rUnitCost = 2.2;
 // FftTuning::family: the default takes fir_fft32r at L = 32 768 and the
 // LDS-column kernel at L = 16 384; kFamilyLds the LDS-column kernels at both.
 // (Family 2, round 5's L = 16 384 two-workgroups-per-CU register kernel, is a
-// variant patch now: scripts/variants/r16_kernel.patch, not faster on any
+// variant patch now: scripts/variants/r16/r16_kernel.patch, not faster on any
 // config.)
 constexpr int kFamilyDefault = 0, kFamilyLds = 1;
 inline bool fft_reg32(int L, int parts, bool sym, const FftTuning &tune = FftTuning{}) {
