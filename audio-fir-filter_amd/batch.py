@@ -522,3 +522,146 @@ def torch_allreduce_max(group=None):
     def f(peaks):
         dist.all_reduce(peaks, op=dist.ReduceOp.MAX, group=group)
     return f
+
+
+# -- item sets: a batch of files of different lengths in few launches ------------
+class ItemBackend:
+    """What ItemBatch needs from an item set (device, or a test's stub)."""
+
+    def create(self, nframes: Sequence[int], nch: Sequence[int]) -> dict:
+        """Plan and allocate; returns {"file_offset", "file_stride" (per file,
+        floats; stride 0 = no rows), "arena_floats", "groups", "launches"}."""
+        raise NotImplementedError
+
+    def load(self, arena):
+        """the whole input arena ([arena_floats] float32, host) in one copy"""
+        raise NotImplementedError
+
+    def new_peaks(self, nfiles: int):
+        raise NotImplementedError
+
+    def zero_peaks(self, peaks):
+        raise NotImplementedError
+
+    def filter(self, peaks):
+        """every file filtered; file f's max|y| over its channels into peaks[f]"""
+        raise NotImplementedError
+
+    def normalize(self, peaks, force: bool):
+        """file f rescaled by 1 / peaks[f] iff peaks[f] > 1 or force"""
+        raise NotImplementedError
+
+    def rows(self, offset: int, nch: int, stride: int, n: int):
+        """[nch][n] view of a file's block of the output arena"""
+        raise NotImplementedError
+
+
+class ItemBatch:
+    """A batch of files of different lengths and channel counts through one
+    item set (lcfir.ItemSet): one upload of the whole arena, then per step one
+    filter launch per group of equal unit count, one ragged peak launch and one
+    ragged normalize launch, whatever the number of files.  The per-file
+    results are what BatchRunner gives for the same files, bit for bit
+    (ProcessFile.cp:91-101 per file: rescale iff peak > 1 or `normalize`).
+
+    files: [nch_i][n_i] float32 arrays (numpy, or torch tensors on the host)."""
+
+    def __init__(self, backend: ItemBackend, files: Sequence, normalize: bool = False):
+        import numpy as np
+        self.b = backend
+        self.normalize = normalize
+        arrays = []
+        for f, x in enumerate(files):
+            a = np.asarray(x.numpy() if hasattr(x, "numpy") else x)
+            if a.ndim != 2 or a.dtype != np.float32:
+                raise ValueError(f"file {f}: need a [nch][n] float32 array, got {a.dtype} {a.shape}")
+            arrays.append(a)
+        self.nframes = [int(a.shape[1]) for a in arrays]
+        self.nch = [int(a.shape[0]) for a in arrays]
+        self.layout = backend.create(self.nframes, self.nch)
+        self.offset = [int(o) for o in self.layout["file_offset"]]
+        self.stride = [int(s) for s in self.layout["file_stride"]]
+        # the padding between and behind the rows must be zero: it stands for
+        # x = 0 outside [0, n) in every row's launch
+        arena = np.zeros(int(self.layout["arena_floats"]), np.float32)
+        for a, o, s in zip(arrays, self.offset, self.stride):
+            if s == 0:
+                continue
+            for c in range(a.shape[0]):
+                arena[o + c * s:o + c * s + a.shape[1]] = a[c]
+        backend.load(arena)
+        self.peaks = backend.new_peaks(len(arrays))
+        self.steps = 0
+
+    def step(self):
+        self.b.zero_peaks(self.peaks)
+        self.b.filter(self.peaks)
+        self.b.normalize(self.peaks, self.normalize)
+        self.steps += 1
+
+    def results(self):
+        """Per file, the [nch_i][n_i] outputs of the latest step (views of the
+        output arena; a file without samples gives None)."""
+        return [self.b.rows(o, c, s, n) if s else None
+                for o, c, s, n in zip(self.offset, self.nch, self.stride, self.nframes)]
+
+
+class _DeviceSpan:
+    """`count` float32 at a raw device address, as torch.as_tensor reads it."""
+
+    def __init__(self, ptr: int, count: int):
+        self.__cuda_array_interface__ = {"shape": (count,), "typestr": "<f4", "data": (ptr, False),
+                                         "version": 2}
+
+
+class DeviceItemBackend(ItemBackend):
+    """lcfir.ItemSet on the caller's current torch stream; the arenas are
+    seen as torch tensors (the item set owns them: the views die with it)."""
+
+    def __init__(self, flt, device):
+        import torch
+        import lcfir
+        self.torch, self.lc, self.flt, self.dev = torch, lcfir, flt, device
+        self.items = None
+        self.x = self.y = None
+
+    def _sp(self):
+        return self.torch.cuda.current_stream(self.dev).cuda_stream
+
+    def create(self, nframes, nch):
+        self.items = self.lc.ItemSet(self.flt, nframes, nch)
+        info = self.items.info()
+        blocks = [self.items.file(f) for f in range(len(nframes))]
+        live = [b for b in blocks if b[0] is not None]
+        if live:
+            x0, y0 = min(b[0] for b in live), min(b[1] for b in live)  # the arenas' first rows
+            self.x = self.torch.as_tensor(_DeviceSpan(x0, info["arena_floats"]), device=self.dev)
+            self.y = self.torch.as_tensor(_DeviceSpan(y0, info["arena_floats"]), device=self.dev)
+        return {"file_offset": [(b[0] - x0) // 4 if b[0] is not None else 0 for b in blocks],
+                "file_stride": [b[2] for b in blocks], "arena_floats": info["arena_floats"],
+                "groups": info["groups"], "launches": info["launches"]}
+
+    def load(self, arena):
+        if self.x is not None:
+            self.x.copy_(self.torch.from_numpy(arena))
+
+    def new_peaks(self, nfiles):
+        return self.torch.zeros(max(1, nfiles), dtype=self.torch.float32, device=self.dev)
+
+    def zero_peaks(self, peaks):
+        self.lc.peak_reset_dev(peaks, peaks.numel(), self._sp())
+
+    def filter(self, peaks):
+        self.items.filter_dev(peaks, self._sp())
+
+    def normalize(self, peaks, force):
+        self.items.normalize_dev(peaks, force, self._sp())
+
+    def rows(self, offset, nch, stride, n):
+        return self.y[offset:offset + nch * stride].view(nch, stride)[:, :n]
+
+    def close(self):
+        self.x = self.y = None
+        if self.items is not None:
+            self.items.close()
+            self.items = None

@@ -1,0 +1,204 @@
+// items.hpp -- the ragged passes of an item set (include/lcfir.h,
+// lcfir_items_*): many files of different lengths laid out as rows of one
+// arena, filtered group by group with the ordinary multi-channel launches.
+//
+// A group's launch runs with x_hi = end = N_g, the group's longest row, so a
+// shorter row's outputs [n_f, N_g) hold the filter's ringing tail.  The fused
+// peak would take them in; the per-file post-passes (ProcessFile.cp:91-101)
+// and the codec either side (ProcessFile.cp:40-41, :115-117) therefore get
+// forms that stop at each file's own n_f.  All four walk a flat tile table
+// built on the host when the item set is created:
+//
+//   row passes   (peak, normalize): tile -> (arena offset, floats, file),
+//                                   kItemRowTile floats of one row;
+//   codec passes (decode, encode):  tile -> (first interleaved sample, samples,
+//                                   file), kItemPcmTile samples of one file.
+//
+// Tiles have one size whatever the file, so one launch balances a 60-minute
+// file against a thousand 0.1 s ones, and the launch count does not grow with
+// the rows.  Every row starts 16-byte aligned and every row tile starts a
+// multiple of four floats into its row, so the row passes move float4s;
+// each thread has kItemLoads of them in flight (peak_scale.hpp's reasoning).
+// The sample rules themselves are codec.hpp's and peak_scale.hpp's
+// (decode_one, encode_one, scale_one, wave_max), so every value is the
+// per-file call's bit for bit.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "codec.hpp"
+#include "peak_scale.hpp"
+
+namespace lcfir {
+
+constexpr int kItemThreads = 256;
+constexpr int kItemLoads = 4;                                  // 16-byte loads in flight per thread
+constexpr int kItemRowTile = kItemThreads * kItemLoads * 4;    // floats of a row per tile
+constexpr int kItemPcmLoads = 8;                               // samples in flight per thread
+constexpr int kItemPcmTile = kItemThreads * kItemPcmLoads;     // interleaved samples per tile
+
+struct ItemTile {
+    int64_t first; // row passes: offset of the tile in the arena, floats (a multiple of 4);
+                   // codec passes: the tile's first interleaved sample of its file
+    int32_t count; // floats / samples in the tile (<= the tile size)
+    int32_t file;
+};
+
+// A file's block of rows, as the codec passes need it.
+struct ItemFile {
+    int64_t off;    // arena offset of channel 0, floats
+    int64_t stride; // floats between channels
+    int32_t nch;
+    int32_t pad_;
+};
+
+// Per call: where a file's interleaved payload sits and how it is encoded.
+struct ItemPcm {
+    int64_t byte_off;
+    PcmFormat f;
+};
+
+// max |y| of every file over its channels' [0, n_f): one wave reduction per
+// tile, then one atomicMax on the float's bit pattern per wave and file.
+// NaN is skipped (fmaxf), Inf taken -- peak_kernel's rule.
+__global__ __launch_bounds__(kItemThreads) void items_peak_kernel(const float *__restrict__ y,
+                                                                  const ItemTile *__restrict__ tiles,
+                                                                  int64_t ntiles,
+                                                                  unsigned *__restrict__ peak) {
+    for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        const ItemTile tl = tiles[t];
+        const float *__restrict__ p = y + tl.first;
+        const float4 *__restrict__ p4 = reinterpret_cast<const float4 *>(p);
+        const int n4 = tl.count >> 2;
+        float4 v[kItemLoads];
+#pragma unroll
+        for (int u = 0; u < kItemLoads; ++u) {
+            const int i = (int)threadIdx.x + u * kItemThreads;
+            v[u] = i < n4 ? p4[i] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        }
+        float m = 0.0f;
+        const int r = n4 * 4 + (int)threadIdx.x; // the row's last 1-3 floats
+        if (r < tl.count) m = fabsf(p[r]);
+#pragma unroll
+        for (int u = 0; u < kItemLoads; ++u)
+            m = fmaxf(m, fmaxf(fmaxf(fabsf(v[u].x), fabsf(v[u].y)), fmaxf(fabsf(v[u].z), fabsf(v[u].w))));
+        m = wave_max(m);
+        if ((threadIdx.x & 63) == 0 && m > 0.0f) atomicMax(peak + tl.file, __float_as_uint(m));
+    }
+}
+
+// normalize_kernel's decision and rescale, file by file: rows [0, n_f) of
+// file f become scale_one(y, 1 / peak[f]) iff (peak[f] > 1 or force) and
+// peak[f] > 0.  A tile of a file that stays as it is costs one table entry
+// and one peak load.
+__global__ __launch_bounds__(kItemThreads) void items_normalize_kernel(float *__restrict__ y,
+                                                                       const ItemTile *__restrict__ tiles,
+                                                                       int64_t ntiles,
+                                                                       const unsigned *__restrict__ peak,
+                                                                       int force) {
+    for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        const ItemTile tl = tiles[t];
+        const float pk = __uint_as_float(peak[tl.file]);
+        if (!(pk > 1.0f || force) || !(pk > 0.0f)) continue;
+        const double gain = 1.0 / (double)pk;
+        float *__restrict__ p = y + tl.first;
+        float4 *__restrict__ p4 = reinterpret_cast<float4 *>(p);
+        const int n4 = tl.count >> 2;
+        float4 v[kItemLoads];
+#pragma unroll
+        for (int u = 0; u < kItemLoads; ++u) {
+            const int i = (int)threadIdx.x + u * kItemThreads;
+            if (i < n4) v[u] = p4[i];
+        }
+#pragma unroll
+        for (int u = 0; u < kItemLoads; ++u) {
+            const int i = (int)threadIdx.x + u * kItemThreads;
+            if (i < n4) {
+                v[u].x = scale_one(v[u].x, gain);
+                v[u].y = scale_one(v[u].y, gain);
+                v[u].z = scale_one(v[u].z, gain);
+                v[u].w = scale_one(v[u].w, gain);
+                p4[i] = v[u];
+            }
+        }
+        const int r = n4 * 4 + (int)threadIdx.x;
+        if (r < tl.count) p[r] = scale_one(p[r], gain);
+    }
+}
+
+// decode_pcm_kernel over every file at once: interleaved sample i of file f
+// (frame i / nch, channel i % nch) goes to the file's row of that channel.
+// Only [0, n_f) of a row is written, so the rows' padding stays zero.
+__global__ __launch_bounds__(kItemThreads) void items_decode_kernel(const uint8_t *__restrict__ in,
+                                                                    const ItemTile *__restrict__ tiles,
+                                                                    int64_t ntiles,
+                                                                    const ItemFile *__restrict__ files,
+                                                                    const ItemPcm *__restrict__ pcm,
+                                                                    float *__restrict__ x) {
+    for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        const ItemTile tl = tiles[t];
+        const ItemFile fl = files[tl.file];
+        const ItemPcm io = pcm[tl.file];
+        const uint8_t *__restrict__ src = in + io.byte_off;
+        float *__restrict__ dst = x + fl.off;
+        uint32_t raw[kItemPcmLoads];
+#pragma unroll
+        for (int u = 0; u < kItemPcmLoads; ++u) {
+            const int k = (int)threadIdx.x + u * kItemThreads;
+            if (k < tl.count) raw[u] = load_bytes(src + (tl.first + k) * io.f.bytes, io.f.bytes, io.f.big_endian);
+        }
+#pragma unroll
+        for (int u = 0; u < kItemPcmLoads; ++u) {
+            const int k = (int)threadIdx.x + u * kItemThreads;
+            if (k < tl.count) {
+                const int64_t i = tl.first + k;
+                const int64_t fr = i / fl.nch;
+                const int ch = (int)(i - fr * fl.nch);
+                dst[(int64_t)ch * fl.stride + fr] = decode_one(raw[u], io.f);
+            }
+        }
+    }
+}
+
+// encode_pcm_scaled_kernel over every file at once: file f's decision comes
+// from its own peak slot, each sample is scaled as items_normalize_kernel
+// would scale it and then encoded; the rows are left unscaled.
+__global__ __launch_bounds__(kItemThreads) void items_encode_scaled_kernel(const float *__restrict__ y,
+                                                                           const ItemTile *__restrict__ tiles,
+                                                                           int64_t ntiles,
+                                                                           const ItemFile *__restrict__ files,
+                                                                           const ItemPcm *__restrict__ pcm,
+                                                                           const unsigned *__restrict__ peak,
+                                                                           int force, uint8_t *__restrict__ out) {
+    for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        const ItemTile tl = tiles[t];
+        const ItemFile fl = files[tl.file];
+        const ItemPcm io = pcm[tl.file];
+        const float pk = __uint_as_float(peak[tl.file]);
+        const bool scale = (pk > 1.0f || force) && pk > 0.0f;
+        const double gain = scale ? 1.0 / (double)pk : 1.0;
+        const float *__restrict__ src = y + fl.off;
+        uint8_t *__restrict__ dst = out + io.byte_off;
+        float v[kItemPcmLoads];
+#pragma unroll
+        for (int u = 0; u < kItemPcmLoads; ++u) {
+            const int k = (int)threadIdx.x + u * kItemThreads;
+            if (k < tl.count) {
+                const int64_t i = tl.first + k;
+                const int64_t fr = i / fl.nch;
+                const int ch = (int)(i - fr * fl.nch);
+                v[u] = src[(int64_t)ch * fl.stride + fr];
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < kItemPcmLoads; ++u) {
+            const int k = (int)threadIdx.x + u * kItemThreads;
+            if (k < tl.count) {
+                const float s = scale ? scale_one(v[u], gain) : v[u];
+                store_bytes(dst + (tl.first + k) * io.f.bytes, encode_one(s, io.f), io.f.bytes, io.f.big_endian);
+            }
+        }
+    }
+}
+
+} // namespace lcfir

@@ -11,7 +11,10 @@
 //     x[start-half, end+half) in, runs the kernel, copies y[start,end) out
 //     (page-locked caller buffers through the device's two link queues, one
 //     per direction, so concurrent calls move data both ways at once);
-//   * device-pointer entry points that never synchronise the host.
+//   * device-pointer entry points that never synchronise the host;
+//   * item sets (lcfir_items_*): the layout of a batch of files of different
+//     lengths, one filter launch per group of equal unit count and the
+//     ragged passes of items.hpp around them.
 // No CPU fallback exists: if the device or the kernels are unusable every
 // call fails with LCFIR_EDEVICE and a message.
 #include "lcfir.h"
@@ -33,6 +36,7 @@
 #include "codec.hpp"
 #include "fir_direct.hpp"
 #include "fir_fft.hpp"
+#include "items.hpp"
 #include "peak_scale.hpp"
 
 struct lcfir_ctx {
@@ -69,6 +73,42 @@ struct lcfir_ctx {
     // previous-file normalizes (lcfir_filter_window_norm_dev): carried inside
     // the filter launch / run as their own pass (lcfir_ctx_nrm_stats)
     std::atomic<int64_t> nrm_fused{0}, nrm_separate{0};
+};
+
+// An item set (lcfir_items_*): the planned layout of a batch of files, its
+// two arenas and the tile tables the ragged passes walk (items.hpp).  Its
+// memory is plain hipMalloc memory of its own: nothing of it passes through
+// the stream-ordered pool the ctx's tables and scratch come from.
+struct lcfir_items {
+    lcfir_ctx *ctx = nullptr;
+    int device = 0;
+    int32_t nfiles = 0;
+    std::vector<int64_t> n, off, stride; // per file: frames, first row's arena offset, row stride (floats)
+    std::vector<int32_t> nch, group;     // per file: channels, group (-1: no rows)
+    struct Launch {
+        int64_t off;    // arena offset of the launch's first row, floats
+        int64_t n_g;    // the group's longest row: x_hi = end of the launch
+        int64_t stride; // S_g
+        int32_t rows;   // <= 65 535
+    };
+    std::vector<Launch> launches;
+    int32_t ngroups = 0;
+    int64_t rows = 0, arena = 0;
+    float *d_in = nullptr, *d_out = nullptr;
+    lcfir::ItemTile *d_row_tiles = nullptr, *d_pcm_tiles = nullptr;
+    int64_t n_row_tiles = 0, n_pcm_tiles = 0;
+    lcfir::ItemFile *d_files = nullptr;
+    // The codec calls' per-call table (payload offset and format per file):
+    // filled into a page-locked slot, copied to d_pcm in stream order.  A slot
+    // is rewritten only once the copy that read it is done (its event).
+    static constexpr int kPcmSlots = 4;
+    lcfir::ItemPcm *d_pcm = nullptr;
+    lcfir::ItemPcm *h_pcm[kPcmSlots] = {};
+    hipEvent_t pcm_done[kPcmSlots] = {};
+    bool pcm_pending[kPcmSlots] = {};
+    int pcm_next = 0;
+    std::mutex mu;
+    std::vector<hipStream_t> used; // every stream a call on this item set went to
 };
 
 namespace {
@@ -1408,6 +1448,362 @@ int lcfir_encode_pcm_scaled_dev(const float *d_in, int64_t in_stride, int32_t nc
                        reinterpret_cast<hipStream_t>(stream), d_in, in_stride, (int)nch, frames, f,
                        reinterpret_cast<const unsigned *>(d_peak), (int)npeak, force ? 1 : 0,
                        reinterpret_cast<uint8_t *>(d_out));
+    LCFIR_HIP(hipGetLastError());
+    return LCFIR_OK;
+}
+
+// ---- item sets ---------------------------------------------------------------
+constexpr int32_t kItemMaxRows = 65535; // rows of one launch (the kernels' grid.y)
+
+struct ItemsPlan {
+    std::vector<int32_t> group;              // per file
+    std::vector<int64_t> off, stride;        // per file
+    std::vector<int64_t> g_n, g_first, g_rows; // per group
+    std::vector<lcfir_items::Launch> launches;
+    int64_t rows = 0, arena = 0;
+};
+
+// The layout rule of lcfir_items_plan (include/lcfir.h).
+static int items_plan(int64_t unit, int32_t nfiles, const int64_t *n, const int32_t *nch, ItemsPlan &pl) {
+    if (unit < 1) return fail(LCFIR_EINVAL, "unit must be >= 1, got %lld", (long long)unit);
+    if (nfiles < 0) return fail(LCFIR_EINVAL, "negative file count");
+    if (nfiles > 0 && (!n || !nch)) return fail(LCFIR_EINVAL, "null argument");
+    pl = ItemsPlan{};
+    pl.group.assign((size_t)nfiles, -1);
+    pl.off.assign((size_t)nfiles, 0);
+    pl.stride.assign((size_t)nfiles, 0);
+    std::vector<int32_t> order;
+    for (int32_t f = 0; f < nfiles; ++f) {
+        if (n[f] < 0 || nch[f] < 0)
+            return fail(LCFIR_EINVAL, "file %d: negative size (n=%lld, nch=%d)", f, (long long)n[f], nch[f]);
+        if (nch[f] > kItemMaxRows)
+            return fail(LCFIR_EINVAL, "file %d: %d channels (at most %d)", f, nch[f], kItemMaxRows);
+        if (n[f] > INT64_MAX - 3) return fail(LCFIR_EINVAL, "file %d: too long", f);
+        if (n[f] > 0 && nch[f] > 0) order.push_back(f);
+    }
+    auto key = [&](int32_t f) { return n[f] / unit + (n[f] % unit != 0); };
+    std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return key(a) < key(b); });
+    for (size_t i = 0; i < order.size();) {
+        size_t j = i;
+        int64_t n_g = 0, rows = 0;
+        for (; j < order.size() && key(order[j]) == key(order[i]); ++j) {
+            n_g = std::max(n_g, n[order[j]]);
+            rows += nch[order[j]];
+        }
+        const int64_t s_g = (n_g + 3) / 4 * 4;
+        int64_t floats = 0, end = 0;
+        if (__builtin_mul_overflow(rows, s_g, &floats) || __builtin_add_overflow(pl.arena, floats, &end) ||
+            end > INT64_MAX / (int64_t)sizeof(float))
+            return fail(LCFIR_EINVAL, "the arena does not fit 63 bits of bytes");
+        const int32_t g = (int32_t)pl.g_n.size();
+        pl.g_n.push_back(n_g);
+        pl.g_first.push_back(pl.rows);
+        pl.g_rows.push_back(rows);
+        int64_t off = pl.arena;
+        lcfir_items::Launch cur{off, n_g, s_g, 0};
+        for (size_t k = i; k < j; ++k) {
+            const int32_t f = order[k];
+            if (cur.rows + nch[f] > kItemMaxRows) { // a file is never cut
+                pl.launches.push_back(cur);
+                cur = lcfir_items::Launch{off, n_g, s_g, 0};
+            }
+            pl.group[(size_t)f] = g;
+            pl.off[(size_t)f] = off;
+            pl.stride[(size_t)f] = s_g;
+            cur.rows += nch[f];
+            off += (int64_t)nch[f] * s_g;
+        }
+        pl.launches.push_back(cur);
+        pl.rows += rows;
+        pl.arena = end;
+        i = j;
+    }
+    return LCFIR_OK;
+}
+
+int lcfir_items_plan(int64_t unit, int32_t nfiles, const int64_t *n, const int32_t *nch, int32_t *file_group,
+                     int64_t *file_offset, int64_t *file_stride, int32_t *ngroups, int64_t *group_n,
+                     int64_t *group_first_row, int64_t *group_rows, int32_t *nlaunches, int64_t *nrows,
+                     int64_t *arena_floats) {
+    ItemsPlan pl;
+    const int rc = items_plan(unit, nfiles, n, nch, pl);
+    if (rc) return rc;
+    if (pl.launches.size() > (size_t)INT32_MAX) return fail(LCFIR_EINVAL, "too many launches");
+    for (int32_t f = 0; f < nfiles; ++f) {
+        if (file_group) file_group[f] = pl.group[(size_t)f];
+        if (file_offset) file_offset[f] = pl.off[(size_t)f];
+        if (file_stride) file_stride[f] = pl.stride[(size_t)f];
+    }
+    for (size_t g = 0; g < pl.g_n.size(); ++g) {
+        if (group_n) group_n[g] = pl.g_n[g];
+        if (group_first_row) group_first_row[g] = pl.g_first[g];
+        if (group_rows) group_rows[g] = pl.g_rows[g];
+    }
+    if (ngroups) *ngroups = (int32_t)pl.g_n.size();
+    if (nlaunches) *nlaunches = (int32_t)pl.launches.size();
+    if (nrows) *nrows = pl.rows;
+    if (arena_floats) *arena_floats = pl.arena;
+    return LCFIR_OK;
+}
+
+static void items_note_stream(lcfir_items *it, hipStream_t s) {
+    std::lock_guard<std::mutex> lk(it->mu);
+    for (hipStream_t u : it->used)
+        if (u == s) return;
+    it->used.push_back(s);
+}
+
+// blocks of a tile-walking pass (items.hpp): a few per CU, grid-stride beyond
+static unsigned items_blocks(int64_t ntiles) {
+    return (unsigned)std::max<int64_t>(1, std::min<int64_t>(ntiles, (int64_t)device_cus() * 8));
+}
+
+// a device copy of a host table, queued on s (the caller waits for s before src dies)
+static int items_upload(void **d, const void *src, size_t bytes, hipStream_t s) {
+    *d = nullptr;
+    if (bytes == 0) return LCFIR_OK;
+    if (hipMalloc(d, bytes) != hipSuccess)
+        return fail(LCFIR_ENOMEM, "hipMalloc(%zu bytes) for an item table failed", bytes);
+    LCFIR_HIP(hipMemcpyAsync(*d, src, bytes, hipMemcpyHostToDevice, s));
+    return LCFIR_OK;
+}
+
+int lcfir_items_create(lcfir_ctx *ctx, const int64_t *n, const int32_t *nch, int32_t nfiles, lcfir_items **out) {
+    if (!out) return fail(LCFIR_EINVAL, "out is null");
+    *out = nullptr;
+    if (!ctx) return fail(LCFIR_EINVAL, "ctx is null");
+    if (nfiles < 0 || (nfiles > 0 && (!n || !nch))) return fail(LCFIR_EINVAL, "null or negative argument");
+    DeviceGuard g(ctx->device);
+    if (!g.ok) return fail(LCFIR_EDEVICE, "hipSetDevice(%d) failed", ctx->device);
+    int64_t unit = kDirR * kDirNT; // the direct kernel's tile of outputs
+    if (resolve_method(ctx) == LCFIR_METHOD_FFT) {
+        const int rc = ensure_fft(ctx);
+        if (rc) return rc;
+        unit = ctx->fft.B;
+    }
+    ItemsPlan pl;
+    int rc = items_plan(unit, nfiles, n, nch, pl);
+    if (rc) return rc;
+    // the passes' tile tables (items.hpp): fixed-size pieces of every row / of
+    // every file's interleaved samples
+    std::vector<lcfir::ItemTile> row_tiles, pcm_tiles;
+    std::vector<lcfir::ItemFile> files((size_t)nfiles);
+    for (int32_t f = 0; f < nfiles; ++f) {
+        files[(size_t)f] = lcfir::ItemFile{pl.off[(size_t)f], pl.stride[(size_t)f], nch[f], 0};
+        if (pl.group[(size_t)f] < 0) continue;
+        for (int32_t c = 0; c < nch[f]; ++c)
+            for (int64_t t0 = 0; t0 < n[f]; t0 += lcfir::kItemRowTile)
+                row_tiles.push_back({pl.off[(size_t)f] + c * pl.stride[(size_t)f] + t0,
+                                     (int32_t)std::min<int64_t>(lcfir::kItemRowTile, n[f] - t0), f});
+        const int64_t total = n[f] * nch[f]; // <= the arena: no overflow
+        for (int64_t t0 = 0; t0 < total; t0 += lcfir::kItemPcmTile)
+            pcm_tiles.push_back({t0, (int32_t)std::min<int64_t>(lcfir::kItemPcmTile, total - t0), f});
+    }
+    auto *it = new lcfir_items;
+    it->ctx = ctx;
+    it->device = ctx->device;
+    it->nfiles = nfiles;
+    it->n.assign(n, n + nfiles);
+    it->nch.assign(nch, nch + nfiles);
+    it->group = pl.group;
+    it->off = pl.off;
+    it->stride = pl.stride;
+    it->launches = pl.launches;
+    it->ngroups = (int32_t)pl.g_n.size();
+    it->rows = pl.rows;
+    it->arena = pl.arena;
+    it->n_row_tiles = (int64_t)row_tiles.size();
+    it->n_pcm_tiles = (int64_t)pcm_tiles.size();
+    // Plain hipMalloc, not the stream-ordered pool the ctx's tables and scratch
+    // recycle: the arenas are large, live as long as the batch and are handed
+    // to the caller, and creating an item set is no hot path.
+    hipStream_t up = nullptr; // the uploads' stream, gone again when create returns
+    auto build = [&]() -> int {
+        LCFIR_HIP(hipStreamCreateWithFlags(&up, hipStreamNonBlocking));
+        if (it->arena > 0) {
+            const size_t bytes = sizeof(float) * (size_t)it->arena;
+            if (hipMalloc(reinterpret_cast<void **>(&it->d_in), bytes) != hipSuccess ||
+                hipMalloc(reinterpret_cast<void **>(&it->d_out), bytes) != hipSuccess)
+                return fail(LCFIR_ENOMEM, "hipMalloc for two arenas of %lld floats failed", (long long)it->arena);
+            LCFIR_HIP(hipMemsetAsync(it->d_in, 0, bytes, up));
+        }
+        int r = items_upload(reinterpret_cast<void **>(&it->d_row_tiles), row_tiles.data(),
+                             row_tiles.size() * sizeof(lcfir::ItemTile), up);
+        if (!r)
+            r = items_upload(reinterpret_cast<void **>(&it->d_pcm_tiles), pcm_tiles.data(),
+                             pcm_tiles.size() * sizeof(lcfir::ItemTile), up);
+        if (!r)
+            r = items_upload(reinterpret_cast<void **>(&it->d_files), files.data(),
+                             files.size() * sizeof(lcfir::ItemFile), up);
+        if (r) return r;
+        if (nfiles > 0) {
+            const size_t tb = sizeof(lcfir::ItemPcm) * (size_t)nfiles;
+            if (hipMalloc(reinterpret_cast<void **>(&it->d_pcm), tb) != hipSuccess)
+                return fail(LCFIR_ENOMEM, "hipMalloc for the codec table failed");
+            for (int k = 0; k < lcfir_items::kPcmSlots; ++k) {
+                if (hipHostMalloc(reinterpret_cast<void **>(&it->h_pcm[k]), tb, hipHostMallocDefault) != hipSuccess)
+                    return fail(LCFIR_ENOMEM, "hipHostMalloc for the codec table failed");
+                LCFIR_HIP(hipEventCreateWithFlags(&it->pcm_done[k], hipEventDisableTiming));
+            }
+        }
+        LCFIR_HIP(hipStreamSynchronize(up));
+        return LCFIR_OK;
+    };
+    rc = build();
+    if (up) { // the host tables above die with this call: nothing of theirs may stay queued
+        (void)hipStreamSynchronize(up);
+        (void)hipStreamDestroy(up);
+    }
+    if (rc) {
+        const std::string keep = g_err;
+        lcfir_items_destroy(it);
+        g_err = keep;
+        return rc;
+    }
+    *out = it;
+    return LCFIR_OK;
+}
+
+int lcfir_items_destroy(lcfir_items *it) {
+    if (!it) return LCFIR_OK;
+    DeviceGuard g(it->device);
+    for (hipStream_t s : it->used) (void)hipStreamSynchronize(s);
+    void *bufs[] = {it->d_in, it->d_out, it->d_row_tiles, it->d_pcm_tiles, it->d_files, it->d_pcm};
+    for (void *p : bufs)
+        if (p) (void)hipFree(p);
+    for (int k = 0; k < lcfir_items::kPcmSlots; ++k) {
+        if (it->h_pcm[k]) (void)hipHostFree(it->h_pcm[k]);
+        if (it->pcm_done[k]) (void)hipEventDestroy(it->pcm_done[k]);
+    }
+    delete it;
+    return LCFIR_OK;
+}
+
+int lcfir_items_file(const lcfir_items *it, int32_t f, float **d_x, float **d_y, int64_t *stride) {
+    if (!it || !d_x || !d_y || !stride) return fail(LCFIR_EINVAL, "null argument");
+    if (f < 0 || f >= it->nfiles) return fail(LCFIR_EINVAL, "file %d out of range (%d files)", f, it->nfiles);
+    const bool has = it->group[(size_t)f] >= 0;
+    *d_x = has ? it->d_in + it->off[(size_t)f] : nullptr;
+    *d_y = has ? it->d_out + it->off[(size_t)f] : nullptr;
+    *stride = it->stride[(size_t)f];
+    return LCFIR_OK;
+}
+
+int lcfir_items_info(const lcfir_items *it, int32_t *groups, int32_t *launches, int64_t *rows,
+                     int64_t *arena_floats) {
+    if (!it || !groups || !launches || !rows || !arena_floats) return fail(LCFIR_EINVAL, "null argument");
+    *groups = it->ngroups;
+    *launches = (int32_t)it->launches.size();
+    *rows = it->rows;
+    *arena_floats = it->arena;
+    return LCFIR_OK;
+}
+
+int lcfir_items_filter_dev(lcfir_items *it, float *d_peak, void *stream) {
+    if (!it) return fail(LCFIR_EINVAL, "items is null");
+    DeviceGuard g(it->device);
+    if (!g.ok) return fail(LCFIR_EDEVICE, "hipSetDevice(%d) failed", it->device);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    items_note_stream(it, s);
+    for (const lcfir_items::Launch &l : it->launches) {
+        lcfir::DirectParams p{};
+        p.x = it->d_in + l.off;
+        p.x_lo = 0;
+        p.x_hi = l.n_g;
+        p.x_stride = l.stride;
+        p.y = it->d_out + l.off;
+        p.y_lo = 0;
+        p.y_stride = l.stride;
+        p.start = 0;
+        p.end = l.n_g;
+        p.peak = nullptr; // the tails [n_f, N_g) must not enter a file's peak
+        p.peak_stride = 1;
+        const int rc = run_filter(it->ctx, p, l.rows, s);
+        if (rc) return rc;
+    }
+    if (d_peak && it->n_row_tiles > 0) {
+        hipLaunchKernelGGL(lcfir::items_peak_kernel, dim3(items_blocks(it->n_row_tiles)), dim3(lcfir::kItemThreads),
+                           0, s, it->d_out, it->d_row_tiles, it->n_row_tiles, peak_bits(d_peak));
+        LCFIR_HIP(hipGetLastError());
+    }
+    return LCFIR_OK;
+}
+
+int lcfir_items_normalize_dev(lcfir_items *it, const float *d_peak, int force, void *stream) {
+    if (!it || !d_peak) return fail(LCFIR_EINVAL, "null argument");
+    if (it->n_row_tiles == 0) return LCFIR_OK;
+    DeviceGuard g(it->device);
+    if (!g.ok) return fail(LCFIR_EDEVICE, "hipSetDevice(%d) failed", it->device);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    items_note_stream(it, s);
+    hipLaunchKernelGGL(lcfir::items_normalize_kernel, dim3(items_blocks(it->n_row_tiles)),
+                       dim3(lcfir::kItemThreads), 0, s, it->d_out, it->d_row_tiles, it->n_row_tiles,
+                       reinterpret_cast<const unsigned *>(d_peak), force ? 1 : 0);
+    LCFIR_HIP(hipGetLastError());
+    return LCFIR_OK;
+}
+
+// Fill the next page-locked slot with the call's per-file table and queue its
+// copy to d_pcm on s.
+static int items_pcm_table(lcfir_items *it, const int64_t *byte_offset, const int32_t *format, hipStream_t s) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs == hipStreamCaptureStatusActive)
+        return fail(LCFIR_EINVAL, "the item set's codec calls cannot be captured into a HIP graph");
+    std::lock_guard<std::mutex> lk(it->mu);
+    const int k = it->pcm_next;
+    if (it->pcm_pending[k]) LCFIR_HIP(hipEventSynchronize(it->pcm_done[k]));
+    it->pcm_pending[k] = false;
+    for (int32_t f = 0; f < it->nfiles; ++f) {
+        lcfir::ItemPcm e{0, {2, false, false}};
+        if (it->group[(size_t)f] >= 0) {
+            if (!pcm_format(format[f], e.f))
+                return fail(LCFIR_EINVAL, "file %d: unknown PCM format %d", f, format[f]);
+            if (byte_offset[f] < 0) return fail(LCFIR_EINVAL, "file %d: negative byte offset", f);
+            e.byte_off = byte_offset[f];
+        }
+        it->h_pcm[k][f] = e;
+    }
+    LCFIR_HIP(hipMemcpyAsync(it->d_pcm, it->h_pcm[k], sizeof(lcfir::ItemPcm) * (size_t)it->nfiles,
+                             hipMemcpyHostToDevice, s));
+    LCFIR_HIP(hipEventRecord(it->pcm_done[k], s));
+    it->pcm_pending[k] = true;
+    it->pcm_next = (k + 1) % lcfir_items::kPcmSlots;
+    return LCFIR_OK;
+}
+
+int lcfir_items_decode_pcm_dev(lcfir_items *it, const void *d_bytes, const int64_t *byte_offset,
+                               const int32_t *format, void *stream) {
+    if (!it) return fail(LCFIR_EINVAL, "items is null");
+    if (it->n_pcm_tiles == 0) return LCFIR_OK;
+    if (!d_bytes || !byte_offset || !format) return fail(LCFIR_EINVAL, "null argument");
+    DeviceGuard g(it->device);
+    if (!g.ok) return fail(LCFIR_EDEVICE, "hipSetDevice(%d) failed", it->device);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int rc = items_pcm_table(it, byte_offset, format, s);
+    if (rc) return rc;
+    items_note_stream(it, s);
+    hipLaunchKernelGGL(lcfir::items_decode_kernel, dim3(items_blocks(it->n_pcm_tiles)), dim3(lcfir::kItemThreads),
+                       0, s, reinterpret_cast<const uint8_t *>(d_bytes), it->d_pcm_tiles, it->n_pcm_tiles,
+                       it->d_files, it->d_pcm, it->d_in);
+    LCFIR_HIP(hipGetLastError());
+    return LCFIR_OK;
+}
+
+int lcfir_items_encode_pcm_scaled_dev(lcfir_items *it, const float *d_peak, int force, void *d_bytes,
+                                      const int64_t *byte_offset, const int32_t *format, void *stream) {
+    if (!it) return fail(LCFIR_EINVAL, "items is null");
+    if (it->n_pcm_tiles == 0) return LCFIR_OK;
+    if (!d_peak || !d_bytes || !byte_offset || !format) return fail(LCFIR_EINVAL, "null argument");
+    DeviceGuard g(it->device);
+    if (!g.ok) return fail(LCFIR_EDEVICE, "hipSetDevice(%d) failed", it->device);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int rc = items_pcm_table(it, byte_offset, format, s);
+    if (rc) return rc;
+    items_note_stream(it, s);
+    hipLaunchKernelGGL(lcfir::items_encode_scaled_kernel, dim3(items_blocks(it->n_pcm_tiles)),
+                       dim3(lcfir::kItemThreads), 0, s, it->d_out, it->d_pcm_tiles, it->n_pcm_tiles, it->d_files,
+                       it->d_pcm, reinterpret_cast<const unsigned *>(d_peak), force ? 1 : 0,
+                       reinterpret_cast<uint8_t *>(d_bytes));
     LCFIR_HIP(hipGetLastError());
     return LCFIR_OK;
 }

@@ -107,6 +107,17 @@ _SIGNATURES = {
     "lcfir_encode_pcm_dev": ([_vp, _c_i64, _c_i32, _c_i64, _c_int, _vp, _vp], _c_int),
     "lcfir_encode_pcm_scaled_dev": ([_vp, _c_i64, _c_i32, _c_i64, _c_int, _vp, _c_i32, _c_int, _vp, _vp],
                                     _c_int),
+    "lcfir_items_plan": ([_c_i64, _c_i32, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(_c_i32), _vp, _vp, _vp,
+                          ctypes.POINTER(_c_i32), ctypes.POINTER(_c_i64), ctypes.POINTER(_c_i64)], _c_int),
+    "lcfir_items_create": ([_ctxp, _vp, _vp, _c_i32, ctypes.POINTER(_vp)], _c_int),
+    "lcfir_items_destroy": ([_vp], _c_int),
+    "lcfir_items_file": ([_vp, _c_i32, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_c_i64)], _c_int),
+    "lcfir_items_info": ([_vp, ctypes.POINTER(_c_i32), ctypes.POINTER(_c_i32), ctypes.POINTER(_c_i64),
+                          ctypes.POINTER(_c_i64)], _c_int),
+    "lcfir_items_filter_dev": ([_vp, _vp, _vp], _c_int),
+    "lcfir_items_normalize_dev": ([_vp, _vp, _c_int, _vp], _c_int),
+    "lcfir_items_decode_pcm_dev": ([_vp, _vp, _vp, _vp, _vp], _c_int),
+    "lcfir_items_encode_pcm_scaled_dev": ([_vp, _vp, _c_int, _vp, _vp, _vp, _vp], _c_int),
     "lcfir_dev_malloc": ([_c_int, ctypes.c_size_t, ctypes.POINTER(_vp)], _c_int),
     "lcfir_dev_free": ([_vp], _c_int),
     "lcfir_memcpy_h2d": ([_vp, _vp, ctypes.c_size_t, _vp], _c_int),
@@ -344,6 +355,106 @@ def _filter_window_norm_dev(self, d_xw, x_lo: int, x_hi: int, x_stride: int, n: 
 
 Filter.filter_window_dev = _filter_window_dev
 Filter.filter_window_norm_dev = _filter_window_norm_dev
+
+
+class ItemSet:
+    """lcfir_items_*: a batch of files of different lengths (the reference's
+    batch scenario, main.cp:132-147) laid out as zero-padded rows of one arena
+    and filtered in one launch per group of equal unit count, with ragged
+    peak / normalize / codec passes of one launch each.  `nframes[f]` frames
+    and `nch[f]` channels per file.  Serves one stream at a time."""
+
+    def __init__(self, flt: "Filter", nframes, nch):
+        lib = load()
+        self._n = np.ascontiguousarray(np.asarray(nframes, dtype=np.int64).reshape(-1))
+        self._nch = np.ascontiguousarray(np.asarray(nch, dtype=np.int32).reshape(-1))
+        if self._n.size != self._nch.size:
+            raise ValueError("nframes and nch differ in length")
+        self.flt = flt  # the ctx must outlive the item set's filter calls
+        self.nfiles = int(self._n.size)
+        h = ctypes.c_void_p()
+        _check(lib.lcfir_items_create(flt.ctx, self._n.ctypes.data, self._nch.ctypes.data, self.nfiles,
+                                      ctypes.byref(h)))
+        self._h = h
+
+    @staticmethod
+    def plan(unit: int, nframes, nch) -> dict:
+        """lcfir_items_plan, the pure layout rule (no device): per file its
+        group (-1: no rows), first row's arena offset in floats and stride;
+        per group N_g, first row and row count; launches, rows, arena floats."""
+        n = np.ascontiguousarray(np.asarray(nframes, dtype=np.int64).reshape(-1))
+        c = np.ascontiguousarray(np.asarray(nch, dtype=np.int32).reshape(-1))
+        if n.size != c.size:
+            raise ValueError("nframes and nch differ in length")
+        nf = int(n.size)
+        fg = np.zeros(nf, np.int32)
+        fo, fs = np.zeros(nf, np.int64), np.zeros(nf, np.int64)
+        gn, gf, gr = np.zeros(nf, np.int64), np.zeros(nf, np.int64), np.zeros(nf, np.int64)
+        ng, nl = ctypes.c_int32(), ctypes.c_int32()
+        rows, arena = ctypes.c_int64(), ctypes.c_int64()
+        _check(load().lcfir_items_plan(int(unit), nf, n.ctypes.data, c.ctypes.data, fg.ctypes.data, fo.ctypes.data,
+                                       fs.ctypes.data, ctypes.byref(ng), gn.ctypes.data, gf.ctypes.data,
+                                       gr.ctypes.data, ctypes.byref(nl), ctypes.byref(rows), ctypes.byref(arena)))
+        g = ng.value
+        return {"file_group": fg, "file_offset": fo, "file_stride": fs, "group_n": gn[:g].copy(),
+                "group_first_row": gf[:g].copy(), "group_rows": gr[:g].copy(), "groups": g,
+                "launches": nl.value, "rows": rows.value, "arena_floats": arena.value}
+
+    def file(self, f: int):
+        """(d_x, d_y, stride): file f's rows in the input and output arenas as
+        raw device addresses (None, None, 0 for a file without rows).  Write
+        only [0, n_f) of each input row."""
+        dx, dy, st = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_int64()
+        _check(load().lcfir_items_file(self._h, int(f), ctypes.byref(dx), ctypes.byref(dy), ctypes.byref(st)))
+        return dx.value, dy.value, st.value
+
+    def info(self) -> dict:
+        g, l_ = ctypes.c_int32(), ctypes.c_int32()
+        r, a = ctypes.c_int64(), ctypes.c_int64()
+        _check(load().lcfir_items_info(self._h, ctypes.byref(g), ctypes.byref(l_), ctypes.byref(r), ctypes.byref(a)))
+        return {"groups": g.value, "launches": l_.value, "rows": r.value, "arena_floats": a.value}
+
+    def filter_dev(self, d_peak=None, stream=0):
+        """Every file filtered; d_peak (nfiles floats, zeroed by the caller)
+        receives each file's max|y| over its channels and [0, n_f)."""
+        _check(load().lcfir_items_filter_dev(self._h, _ptr(d_peak) if d_peak is not None else None,
+                                             stream or None))
+
+    def normalize_dev(self, d_peak, force: bool = False, stream=0):
+        _check(load().lcfir_items_normalize_dev(self._h, _ptr(d_peak), 1 if force else 0, stream or None))
+
+    def _pcm_args(self, byte_offset, formats):
+        off = np.ascontiguousarray(np.asarray(byte_offset, dtype=np.int64).reshape(-1))
+        fmt = np.ascontiguousarray(np.asarray([PCM_FORMATS[f] if isinstance(f, str) else int(f) for f in formats],
+                                              dtype=np.int32))
+        if off.size != self.nfiles or fmt.size != self.nfiles:
+            raise ValueError("byte_offset and formats need one entry per file")
+        return off, fmt
+
+    def decode_pcm_dev(self, d_bytes, byte_offset, formats, stream=0):
+        """Interleaved PCM payloads (file f's at d_bytes + byte_offset[f], in
+        formats[f]) -> every file's input rows, one launch."""
+        off, fmt = self._pcm_args(byte_offset, formats)
+        _check(load().lcfir_items_decode_pcm_dev(self._h, _ptr(d_bytes), off.ctypes.data, fmt.ctypes.data,
+                                                 stream or None))
+
+    def encode_pcm_scaled_dev(self, d_peak, force: bool, d_bytes, byte_offset, formats, stream=0):
+        """Every file's output rows -> interleaved PCM, each file scaled by its
+        own peak slot as encode_pcm_scaled_dev would; one launch."""
+        off, fmt = self._pcm_args(byte_offset, formats)
+        _check(load().lcfir_items_encode_pcm_scaled_dev(self._h, _ptr(d_peak), 1 if force else 0, _ptr(d_bytes),
+                                                        off.ctypes.data, fmt.ctypes.data, stream or None))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            load().lcfir_items_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class ThreadSafeProgress:

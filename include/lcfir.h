@@ -353,6 +353,89 @@ int lcfir_encode_pcm_scaled_dev(const float *d_in, int64_t in_stride, int32_t nc
                                 int format, const float *d_peak, int32_t npeak, int force,
                                 void *d_out, void *stream);
 
+/* ---- item sets: a batch of files of different lengths in few launches ---- */
+/* The reference's batch scenario (main.cp:132-147) filters many files one
+ * after another.  Every entry point above takes channels that share one
+ * length, so a library of short files costs a launch per file.  An item set
+ * lays the files' channels out as rows of one arena, zero-padded, grouped by
+ * the number of work units their length needs, and filters each group with
+ * one ordinary multi-channel launch: a row of n samples followed by physical
+ * zeros, filtered with x_hi = end = N_g >= n, gives outputs [0, n) that are
+ * bit-identical to the per-file call's (x = 0 outside [0, N) above; the
+ * segment grid is anchored at output 0 of every row).  Outputs [n, N_g) of a
+ * shorter row hold the filter's ringing tail, so the peak, the normalize and
+ * the codec have forms of their own here that stop at each file's n.
+ *
+ * lcfir_items_plan: the layout rule, a pure function (no device).
+ *   key     k = ceil(n / unit); files with n = 0 or nch = 0 get no rows
+ *           (group -1, offset 0, stride 0);
+ *   order   groups in ascending k, files within a group in input order;
+ *   block   a file's nch rows are contiguous at its group's stride
+ *           S_g = N_g rounded up to 4 floats, N_g = the group's largest n:
+ *           an (nch, S_g) block the per-file calls accept as it is;
+ *   align   every group, so every row, starts a multiple of 4 floats (16 B)
+ *           into the arena;
+ *   cut     a group of more than 65 535 rows runs as consecutive launches
+ *           of whole files (nch > 65 535 is LCFIR_EINVAL).
+ * Outputs, each nullable: per file (nfiles entries) its group, its first
+ * row's arena offset in floats, its stride; per group (up to nfiles entries,
+ * *ngroups written) N_g, the group's first row (rows numbered in arena
+ * order) and its row count; the launch, row and arena-float totals.
+ * Correctness never depends on the grouping (any N_g >= n gives the same
+ * bytes; it only decides how many padded units run), so a plan made before
+ * lcfir_ctx_set_fft_tuning / _set_method / _set_fft_family stays valid. */
+int lcfir_items_plan(int64_t unit, int32_t nfiles, const int64_t *n, const int32_t *nch,
+                     int32_t *file_group, int64_t *file_offset, int64_t *file_stride,
+                     int32_t *ngroups, int64_t *group_n, int64_t *group_first_row, int64_t *group_rows,
+                     int32_t *nlaunches, int64_t *nrows, int64_t *arena_floats);
+
+typedef struct lcfir_items lcfir_items;
+/* Plans nfiles files (n[f] frames, nch[f] channels) with unit = the outputs
+ * per work unit of the ctx's method as resolved now (lcfir_ctx_fft_units'
+ * *outputs for the FFT method, 4 096 for the direct form), allocates an input
+ * and an output arena of the planned length on the ctx's device, zeroes the
+ * input arena once and uploads the tile tables the passes below walk.  The
+ * ctx must outlive the item set's lcfir_items_filter_dev calls.  An item set
+ * serves one stream at a time: calls on one stream run in order; the caller
+ * orders a change of stream itself. */
+int lcfir_items_create(lcfir_ctx *ctx, const int64_t *n, const int32_t *nch, int32_t nfiles,
+                       lcfir_items **out);
+/* Waits for the streams the item set launched on, then frees its memory. */
+int lcfir_items_destroy(lcfir_items *items);
+/* File f's block of rows in each arena: channel c at *d_x + c * *stride
+ * (input) and *d_y + c * *stride (output); NULL, NULL, 0 for a file without
+ * rows.  The caller writes ONLY [0, n_f) of each input row: the zeros
+ * behind them are what makes a row's outputs the per-file call's.  Output
+ * rows hold the result in [0, n_f) and unspecified values beyond. */
+int lcfir_items_file(const lcfir_items *items, int32_t f, float **d_x, float **d_y, int64_t *stride);
+int lcfir_items_info(const lcfir_items *items, int32_t *groups, int32_t *launches, int64_t *rows,
+                     int64_t *arena_floats);
+/* Filters every file: one multi-channel launch per group launch (x_hi = end
+ * = N_g, no fused peak), then, if d_peak is non-NULL, one launch that max-es
+ * each file's max|y| over its channels and over [0, n_f) only into
+ * d_peak[f] (nfiles floats, zeroed by the caller as for
+ * lcfir_filter_channels_dev; NaN skipped, Inf taken).  Allocates nothing
+ * beyond what the filter launches do, so it captures into a HIP graph under
+ * their rule (an eager call on the stream first sizes the FFT scratch). */
+int lcfir_items_filter_dev(lcfir_items *items, float *d_peak, void *stream);
+/* One launch: file f's output rows [0, n_f) become
+ * (float)((double)y * (1.0 / (double)d_peak[f])) iff (d_peak[f] > 1 or
+ * force) and d_peak[f] > 0 -- lcfir_normalize_dev per file with npeak = 1
+ * and the file's own slot, bit for bit. */
+int lcfir_items_normalize_dev(lcfir_items *items, const float *d_peak, int force, void *stream);
+/* One launch each: lcfir_decode_pcm_dev into every file's input rows /
+ * lcfir_encode_pcm_scaled_dev (npeak = 1, the file's own slot; the output
+ * rows stay unscaled) from every file's output rows.  d_bytes: one device
+ * buffer holding every file's interleaved payload, file f's at
+ * byte_offset[f] in format[f] (lcfir_pcm_format); byte_offset and format are
+ * host arrays of nfiles entries, copied before the call returns (entries of
+ * files without rows are ignored).  These two calls cannot be captured into a
+ * HIP graph (the per-call table is uploaded from the host). */
+int lcfir_items_decode_pcm_dev(lcfir_items *items, const void *d_bytes, const int64_t *byte_offset,
+                               const int32_t *format, void *stream);
+int lcfir_items_encode_pcm_scaled_dev(lcfir_items *items, const float *d_peak, int force, void *d_bytes,
+                                      const int64_t *byte_offset, const int32_t *format, void *stream);
+
 /* ---- device memory / stream helpers for hosts without a GPU runtime ----- */
 int lcfir_dev_malloc(int device, size_t bytes, void **out);
 int lcfir_dev_free(void *p);
