@@ -533,6 +533,10 @@ class ItemBackend:
         floats; stride 0 = no rows), "arena_floats", "groups", "launches"}."""
         raise NotImplementedError
 
+    def set_fusion(self, mode: str):
+        """"auto" / "groups" (lcfir.ItemSet.set_fusion): how the filter step is
+        launched, never what it computes.  A backend without launches ignores it."""
+
     def load(self, arena):
         """the whole input arena ([arena_floats] float32, host) in one copy"""
         raise NotImplementedError
@@ -559,17 +563,21 @@ class ItemBackend:
 class ItemBatch:
     """A batch of files of different lengths and channel counts through one
     item set (lcfir.ItemSet): one upload of the whole arena, then per step one
-    filter launch per group of equal unit count, one ragged peak launch and one
-    ragged normalize launch, whatever the number of files.  The per-file
+    filter launch per group of equal unit count (fusion="groups", the default)
+    or one for all groups (fusion="auto", where the plan allows), one ragged
+    peak launch and one ragged normalize launch, whatever the number of files.  The per-file
     results are what BatchRunner gives for the same files, bit for bit
     (ProcessFile.cp:91-101 per file: rescale iff peak > 1 or `normalize`).
 
     files: [nch_i][n_i] float32 arrays (numpy, or torch tensors on the host)."""
 
-    def __init__(self, backend: ItemBackend, files: Sequence, normalize: bool = False):
+    def __init__(self, backend: ItemBackend, files: Sequence, normalize: bool = False, fusion: str = "groups"):
         import numpy as np
+        if fusion not in ("auto", "groups"):
+            raise ValueError(f"fusion must be 'auto' or 'groups', got {fusion!r}")
         self.b = backend
         self.normalize = normalize
+        self.fusion = fusion
         arrays = []
         for f, x in enumerate(files):
             a = np.asarray(x.numpy() if hasattr(x, "numpy") else x)
@@ -579,6 +587,7 @@ class ItemBatch:
         self.nframes = [int(a.shape[1]) for a in arrays]
         self.nch = [int(a.shape[0]) for a in arrays]
         self.layout = backend.create(self.nframes, self.nch)
+        backend.set_fusion(fusion)
         self.offset = [int(o) for o in self.layout["file_offset"]]
         self.stride = [int(s) for s in self.layout["file_stride"]]
         # the padding between and behind the rows must be zero: it stands for
@@ -640,6 +649,9 @@ class DeviceItemBackend(ItemBackend):
         return {"file_offset": [(b[0] - x0) // 4 if b[0] is not None else 0 for b in blocks],
                 "file_stride": [b[2] for b in blocks], "arena_floats": info["arena_floats"],
                 "groups": info["groups"], "launches": info["launches"]}
+
+    def set_fusion(self, mode):
+        self.items.set_fusion(mode)
 
     def load(self, arena):
         if self.x is not None:

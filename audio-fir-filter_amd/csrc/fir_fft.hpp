@@ -306,6 +306,54 @@ __host__ __device__ inline int fft_div(int u, const FftGrid &g) {
     return (int)(((uint64_t)(uint32_t)u * g.m) >> g.sh);
 }
 
+// The item form of the single-partition kernels (template flag kItem; item
+// sets, include/lcfir.h lcfir_items_*): the launch's units are the entries of
+// a device table instead of a (channel, segment) grid, so one launch covers
+// rows of any lengths, from any files and groups of an arena.  (The two
+// LDS-column kernels have it; fir_fft32r_kernel does not.)  Entry u gives
+// unit u its own view of the launch parameters (fft_unit_decode): exactly the
+// parameters the per-file call gives that unit, so its stores are that call's
+// bytes and nothing of a row past its file's n is written.
+struct FftItemUnit {
+    int64_t off; // arena offset of the unit's row, floats
+    int32_t seg; // its segment of the row: outputs [seg B, min((seg + 1) B, n))
+    int32_t n;   // frames of the row's file
+};
+static_assert(sizeof(FftItemUnit) == 16, "one 16-byte scalar load per unit");
+// read through the constant address space: the index is wave-uniform, so the
+// entry arrives by scalar loads and the buffer resources built from it stay in
+// SGPRs (no waterfall loops, no vector-memory instruction)
+typedef const __attribute__((address_space(4))) FftItemUnit *fft_item_ptr;
+
+// Unit u of a launch as (view, ch, n0).  Plain form: (ch, n0) from the grid,
+// the view is p itself (`view` stays untouched: callers read `kItem ? view : p`).
+// Item form: p with x = arena_in + off, y = arena_out + off, the ranges
+// x_lo = y_lo = start = seg0 = 0, x_hi = end = n, no fused peak; ch = 0,
+// n0 = seg B.
+template <bool kItem>
+__device__ __forceinline__ void fft_unit_decode(const DirectParams &p, const FftGrid &gd, const FftItemUnit *items,
+                                                int u, int B, DirectParams &view, int &ch, int64_t &n0) {
+    if constexpr (kItem) {
+        // blockIdx, gridDim, the round and gd.units only: uniform, and provably so
+        // (field by field: a struct is not copyable out of the constant space;
+        // the three loads merge into one s_load_dwordx4)
+        const fft_item_ptr e = (fft_item_ptr)items + __builtin_amdgcn_readfirstlane(u);
+        const int64_t off = e->off;
+        const int32_t seg = e->seg, n = e->n;
+        view = p;
+        view.x = p.x + off;
+        view.y = p.y + off;
+        view.x_lo = view.y_lo = view.start = view.seg0 = 0;
+        view.x_hi = view.end = n;
+        view.peak = nullptr;
+        ch = 0;
+        n0 = (int64_t)seg * B;
+    } else {
+        ch = fft_div(u, gd);
+        n0 = p.seg0 + (int64_t)(u - ch * gd.nseg) * B;
+    }
+}
+
 // Task word of thread t = 64 w + lane after exchange 2: task A = (cA, d1A, e1A),
 // task B = (cB, d1B, e1B); bins k = c + 16 (d1 + 8 e1 + 64 e2), e2 = register.
 // Waves 1..7: columns w and 16 - w, B mirrors A, so X[k] (A[e2]) and X[M-k]
@@ -1001,11 +1049,15 @@ __device__ __forceinline__ void fft_columns(double2 *flds, const double2 *twl, c
 //   kFftOutLast  : RNE(p.y64 + partial) to f32 into y, fused peak.
 // c8 = the special lane's bin-M/2 coefficient 2S - 2D of this pair table.
 // kNrm: the launch also rescales a previous file's outputs (FftNrm).
-template <int kOut, bool kNrm = false>
+// kItem: the item form (fft_unit_decode), kFftOutSym and kFftOutF32 without kNrm.
+template <int kOut, bool kNrm = false, bool kItem = false>
 __global__ __launch_bounds__(kFftNT) void fir_fft_f64_kernel(DirectParams p, const double2 *__restrict__ pair,
                                                             const double2 *__restrict__ tw,
                                                             const uint32_t *__restrict__ task, int B,
-                                                            FftGrid gd, double2 c8, FftNrm nrm) {
+                                                            FftGrid gd, double2 c8, FftNrm nrm,
+                                                            const FftItemUnit *items) {
+    static_assert(!kItem || (!kNrm && (kOut == kFftOutSym || kOut == kFftOutF32)),
+                  "item form: single-partition filters, no fused normalize");
     extern __shared__ double2 flds[];
     FFT_USTAMP(0);
     // kNrm: the normalize decision, once per launch (uniform)
@@ -1024,8 +1076,19 @@ __global__ __launch_bounds__(kFftNT) void fir_fft_f64_kernel(DirectParams p, con
     float2 v[16]; // samples of the unit about to start
     {
         const int u = fft_unit32(0, blockIdx.x, gridDim.x, gd.units); // < units: the grid is <= units
-        const int c = fft_div(u, gd);
-        fft_load_unit(p, c, p.seg0 + (int64_t)(u - c * gd.nseg) * B, threadIdx.x, v);
+        // (the plain decode is spelled out at this kernel's three sites: through
+        // fft_unit_decode<false> the kNrm and kFftOutLast instantiations came
+        // out with other register numbers than before the item form existed)
+        DirectParams iv;
+        int c;
+        int64_t n0;
+        if constexpr (kItem) {
+            fft_unit_decode<kItem>(p, gd, items, u, B, iv, c, n0);
+        } else {
+            c = fft_div(u, gd);
+            n0 = p.seg0 + (int64_t)(u - c * gd.nseg) * B;
+        }
+        fft_load_unit(kItem ? iv : p, c, n0, threadIdx.x, v);
     }
     // vmcnt counts loads and stores together, in issue order, and the wait
     // pass merges the loop's entry and back edge path-insensitively.  Both
@@ -1051,8 +1114,16 @@ __global__ __launch_bounds__(kFftNT) void fir_fft_f64_kernel(DirectParams p, con
     int j = threadIdx.x;
     asm volatile("" : "+v"(j));
     const int w = j >> 6; // the wave: its columns {w, 16 - w} (wave 0: {0, 8}), fft_columns
-    const int ch = fft_div(u, gd);
-    const int64_t n0 = p.seg0 + (int64_t)(u - ch * gd.nseg) * B;
+    DirectParams iv; // kItem: this unit's view of the launch
+    int ch;
+    int64_t n0;
+    if constexpr (kItem) {
+        fft_unit_decode<kItem>(p, gd, items, u, B, iv, ch, n0);
+    } else {
+        ch = fft_div(u, gd);
+        n0 = p.seg0 + (int64_t)(u - ch * gd.nseg) * B;
+    }
+    const DirectParams &pu = kItem ? iv : p;
     FFT_STAMP(0);
     FFT_USTAMP(1 + rnd);
 
@@ -1075,7 +1146,7 @@ __global__ __launch_bounds__(kFftNT) void fir_fft_f64_kernel(DirectParams p, con
         // the previous channel's staged peaks (written before this barrier;
         // rewritten at the earliest after the next one)
         if (pk_pending >= 0) {
-            if (threadIdx.x == 0) fft_peak_commit(p, pk_pending, pk_lds);
+            if (threadIdx.x == 0) fft_peak_commit(pu, pk_pending, pk_lds);
             pk_pending = -1;
         }
         FFT_STAMP(4);
@@ -1087,8 +1158,16 @@ __global__ __launch_bounds__(kFftNT) void fir_fft_f64_kernel(DirectParams p, con
         // would keep the old v live across the whole loop body.
         const int un1 = fft_unit32(rnd + 1, blockIdx.x, gridDim.x, gd.units);
         const int un = un1 < gd.units ? un1 : u;
-        const int cn = fft_div(un, gd);
-        fft_load_unit(p, cn, p.seg0 + (int64_t)(un - cn * gd.nseg) * B, j, v);
+        DirectParams nv; // kItem: the next unit's view (another row, file or group)
+        int cn;
+        int64_t nn;
+        if constexpr (kItem) {
+            fft_unit_decode<kItem>(p, gd, items, un, B, nv, cn, nn);
+        } else {
+            cn = fft_div(un, gd);
+            nn = p.seg0 + (int64_t)(un - cn * gd.nseg) * B;
+        }
+        fft_load_unit(kItem ? nv : p, cn, nn, j, v);
     });
     if constexpr (kNrm) {
         // waves 0..3 reach this barrier well before waves 4..7: they spend
@@ -1132,22 +1211,22 @@ __global__ __launch_bounds__(kFftNT) void fir_fft_f64_kernel(DirectParams p, con
         __builtin_amdgcn_s_waitcnt(kVmcntNrm);
     else
         __builtin_amdgcn_s_waitcnt(kVmcnt0);
-    float *yb = p.y + (int64_t)ch * p.y_stride + (p.start - p.y_lo);
+    float *yb = pu.y + (int64_t)ch * pu.y_stride + (pu.start - pu.y_lo);
     const __amdgpu_buffer_rsrc_t ys = __builtin_amdgcn_make_buffer_rsrc(
-        yb, (short)0, (int)((p.end - p.start) * 4), 0x00020000);
+        yb, (short)0, (int)((pu.end - pu.start) * 4), 0x00020000);
     // valid outputs c in [cmin, cmax): [T-1, L) for the causal table, [half,
     // L - half) for the zero-phase one (kSym, fft_plan_build; an odd half
     // makes cmin odd)
     constexpr bool kSym = kOut == kFftOutSym;
-    const int cmin = kSym ? p.half : p.ntaps - 1;
-    const int cmax = kSym ? kFftL - p.half : kFftL;
+    const int cmin = kSym ? pu.half : pu.ntaps - 1;
+    const int cmax = kSym ? kFftL - pu.half : kFftL;
     // (negative for outputs before `start`: the launch's segment grid starts
     // at p.seg0 <= start, fft_launch_group)
-    const int64_t off = n0 - cmin - p.start; // offset (samples) of c[0] from start
-    const int64_t oend = p.end - p.start;
+    const int64_t off = n0 - cmin - pu.start; // offset (samples) of c[0] from start
+    const int64_t oend = pu.end - pu.start;
     float pk = 0.0f;
     if constexpr (kOut == kFftOutF32 || kSym) {
-    if (kSym && (cmin & 1) && n0 >= p.start && n0 + B <= p.end) {
+    if (kSym && (cmin & 1) && n0 >= pu.start && n0 + B <= pu.end) {
         // the zero-phase form of an odd half: every output of this unit is
         // in [start, end), but the ends of [cmin, cmax) split a pair
 #pragma unroll
@@ -1161,7 +1240,7 @@ __global__ __launch_bounds__(kFftNT) void fir_fft_f64_kernel(DirectParams p, con
                                                   kNtStore);
             pk = fmaxf(pk, fmaxf(ok0 ? fabsf(f0) : 0.0f, ok1 ? fabsf(f1) : 0.0f));
         }
-    } else if (n0 >= p.start && n0 + B <= p.end) {
+    } else if (n0 >= pu.start && n0 + B <= pu.end) {
         // every output of this unit is in [start, end) and cmin, cmax are
         // even: the pair (c, c+1) is valid iff cmin <= c < cmax, so both
         // stores share one offset and may merge into a dwordx2.  (A resource
@@ -1200,7 +1279,7 @@ __global__ __launch_bounds__(kFftNT) void fir_fft_f64_kernel(DirectParams p, con
         // y64_stride); every output belongs to exactly one unit per launch, so
         // the read-modify-write needs no atomics.  Invalid outputs use an
         // out-of-range offset: their loads return 0 and their stores drop.
-        double *zb = p.y64 + (int64_t)ch * p.y64_stride;
+        double *zb = pu.y64 + (int64_t)ch * pu.y64_stride;
         const __amdgpu_buffer_rsrc_t zs = __builtin_amdgcn_make_buffer_rsrc(
             zb, (short)0, (int)(oend * 8), 0x00020000);
 #pragma unroll
@@ -1235,7 +1314,7 @@ __global__ __launch_bounds__(kFftNT) void fir_fft_f64_kernel(DirectParams p, con
     // the kernel.  Staging follows this unit's second barrier, so thread 0
     // has committed the previous staging (after the first) already.
     if (ch != pk_ch) {
-        if (p.peak && pk_ch >= 0) {
+        if (pu.peak && pk_ch >= 0) {
             fft_peak_stage(pk_lds, pk_run);
             pk_pending = pk_ch;
             asm volatile("" : "+v"(pk_pending)); // a VGPR: SGPRs are the scarcer file here
@@ -1247,7 +1326,7 @@ __global__ __launch_bounds__(kFftNT) void fir_fft_f64_kernel(DirectParams p, con
     FFT_STAMP(14);
     }
     FFT_USTAMP(1 + rnd);
-    if (p.peak && pk_ch >= 0) {
+    if (!kItem && p.peak && pk_ch >= 0) { // the item form has no fused peak (items_peak_kernel)
         __syncthreads();
         if (pk_pending >= 0 && threadIdx.x == 0) fft_peak_commit(p, pk_pending, pk_lds);
         __syncthreads();
@@ -1611,7 +1690,7 @@ inline bool fft32_launch_one(const FftPlan &plan, const DirectParams &q, int par
     }
     hipLaunchKernelGGL((fir_fft32_f64_kernel<kOut>), dim3((unsigned)grid), dim3(kFftNT), fft_lds_bytes(kFft32L), s,
                        q, plan.d_pair + (size_t)part * 2 * kFftPairTable, plan.d_tw, plan.d_task, plan.B,
-                       fft_grid(nseg, units), plan.c8[(size_t)part]);
+                       fft_grid(nseg, units), plan.c8[(size_t)part], (const FftItemUnit *)nullptr);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         err = hipGetErrorString(e);
@@ -1648,11 +1727,11 @@ inline bool fft_launch_one(const FftPlan &plan, const DirectParams &q, int part,
         }
         hipLaunchKernelGGL((fir_fft_f64_kernel<kOut, true>), dim3((unsigned)grid), dim3(kFftNT), fft_lds_bytes(),
                            s, q, plan.d_pair + (size_t)part * kFftPairTable, plan.d_tw, plan.d_task, plan.B, gd,
-                           plan.c8[(size_t)part], nrm);
+                           plan.c8[(size_t)part], nrm, (const FftItemUnit *)nullptr);
     } else
         hipLaunchKernelGGL((fir_fft_f64_kernel<kOut, false>), dim3((unsigned)grid), dim3(kFftNT), fft_lds_bytes(),
                            s, q, plan.d_pair + (size_t)part * kFftPairTable, plan.d_tw, plan.d_task, plan.B, gd,
-                           plan.c8[(size_t)part], FftNrm{});
+                           plan.c8[(size_t)part], FftNrm{}, (const FftItemUnit *)nullptr);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         err = hipGetErrorString(e);
@@ -1817,6 +1896,70 @@ inline bool fft_launch_group(const FftPlan &plan, const DirectParams &p, int nch
             else if (part < plan.parts - 1) ok = fft_launch_one<kFftOutAdd>(plan, qp, part, nch, s, err);
             else ok = fft_launch_one<kFftOutLast>(plan, qp, part, nch, s, err);
             if (!ok) return false;
+        }
+    }
+    return true;
+}
+
+// The item form (fft_unit_decode): can the plan's kernel run units from a table?
+// Single-partition plans on the LDS-column kernels (fir_fft_f64_kernel,
+// fir_fft32_f64_kernel): the partition modes, the fused normalize and the
+// register kernel (fir_fft32r_kernel) have no item instantiation.
+inline bool fft_items_capable(const FftPlan &plan) { return plan.ready && plan.parts == 1 && !plan.reg32; }
+
+// one item-form launch: the kernel's usual LDS size and attribute, grid = min(units, CUs)
+template <auto kKernel, class C8, class... Tail>
+inline void fft_items_launch_kernel(size_t lds, const FftPlan &plan, const DirectParams &q, const FftItemUnit *items,
+                                    int64_t units, hipStream_t s, C8 c8, Tail... tail) {
+    static const bool attr = [lds] {
+        return hipFuncSetAttribute(reinterpret_cast<const void *>(kKernel),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
+    }();
+    (void)attr;
+    const int64_t grid = std::min<int64_t>(units, (int64_t)plan.cus);
+    hipLaunchKernelGGL(kKernel, dim3((unsigned)grid), dim3(kFftNT), lds, s, q, plan.d_pair, plan.d_tw, plan.d_task,
+                       plan.B, fft_grid(1, units) /* the item form reads gd.units only */, c8, tail..., items);
+}
+// Filter the `units` rows x segments of the device table `items` (arena row
+// order, segments ascending) in launches of at most fft_max_units entries: one
+// by default.  p: x / y the arenas' bases, taps / half the filter's, park the
+// stream's slab (L = 32 768 park kernel); every range field comes from the
+// table.  Every row's n is at most fft_chunk_span(plan) (the caller checks), so
+// each unit's view is the per-file call's single chunk.
+inline bool fft_launch_items(const FftPlan &plan, const DirectParams &p, const FftItemUnit *items, int64_t units,
+                             hipStream_t s, std::string &err) {
+    if (units <= 0) return true;
+    if (!fft_items_capable(plan) || !items) {
+        err = "no item form of this plan's kernel";
+        return false;
+    }
+    if (plan.L == kFft32L && !p.park && kParkSlab > 0) {
+        err = "L = 32768 launch without its park slab";
+        return false;
+    }
+    DirectParams q = p;
+    q.ntaps = plan.ntaps;
+    q.peak = nullptr;
+    const int64_t per = fft_max_units(plan);
+    for (int64_t u0 = 0; u0 < units; u0 += per) {
+        const int64_t nu = std::min(per, units - u0);
+        const FftItemUnit *tb = items + u0;
+        if (plan.L == kFft32L && plan.sym)
+            fft_items_launch_kernel<&fir_fft32_f64_kernel<kFftOutSym, true>>(fft_lds_bytes(kFft32L), plan, q, tb, nu,
+                                                                            s, plan.c8[0]);
+        else if (plan.L == kFft32L)
+            fft_items_launch_kernel<&fir_fft32_f64_kernel<kFftOutF32, true>>(fft_lds_bytes(kFft32L), plan, q, tb, nu,
+                                                                            s, plan.c8[0]);
+        else if (plan.sym)
+            fft_items_launch_kernel<&fir_fft_f64_kernel<kFftOutSym, false, true>>(fft_lds_bytes(), plan, q, tb, nu, s,
+                                                                                 plan.c8[0], FftNrm{});
+        else
+            fft_items_launch_kernel<&fir_fft_f64_kernel<kFftOutF32, false, true>>(fft_lds_bytes(), plan, q, tb, nu, s,
+                                                                                 plan.c8[0], FftNrm{});
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) {
+            err = hipGetErrorString(e);
+            return false;
         }
     }
     return true;

@@ -290,18 +290,23 @@ __device__ __forceinline__ void fft32_stage_samples(const DirectParams &p, int c
 // each, fir_fft.hpp's layouts); task: [2][512] task words (E, O); tw:
 // kFft32Tw twiddles; c8: half E's special-lane bin-M/2 coefficient; p.park:
 // gridDim.x x kParkSlab x 512 double2 of slab (fft32_park_doubles).
-template <int kOut>
+// kItem: the item form (fft_unit_decode), single-partition output modes only.
+template <int kOut, bool kItem = false>
 __global__ __launch_bounds__(kFftNT) void fir_fft32_f64_kernel(DirectParams p, const double2 *__restrict__ pair,
                                                               const double2 *__restrict__ tw,
                                                               const uint32_t *__restrict__ task, int B,
-                                                              FftGrid gd, double2 c8) {
+                                                              FftGrid gd, double2 c8, const FftItemUnit *items) {
+    static_assert(!kItem || kOut == kFftOutSym || kOut == kFftOutF32, "item form: single-partition filters");
     extern __shared__ double2 flds[];
     double2 *twl = flds + kFftM; // the kFft32Tw twiddles, LDS-resident
     for (int i = threadIdx.x; i < kFft32Tw; i += kFftNT) twl[i] = tw[i];
     {
         const int u = fft_unit32(0, blockIdx.x, gridDim.x, gd.units);
-        const int c = fft_div(u, gd);
-        fft32_stage_samples(p, c, p.seg0 + (int64_t)(u - c * gd.nseg) * B, threadIdx.x, flds);
+        DirectParams iv;
+        int c;
+        int64_t n0;
+        fft_unit_decode<kItem>(p, gd, items, u, B, iv, c, n0);
+        fft32_stage_samples(kItem ? iv : p, c, n0, threadIdx.x, flds);
     }
     __builtin_amdgcn_s_waitcnt(kVmcnt0);
     __syncthreads();
@@ -317,8 +322,11 @@ __global__ __launch_bounds__(kFftNT) void fir_fft32_f64_kernel(DirectParams p, c
         int j = threadIdx.x;
         asm volatile("" : "+v"(j));
         const int w = j >> 6, lane = j & 63;
-        const int ch = fft_div(u, gd);
-        const int64_t n0 = p.seg0 + (int64_t)(u - ch * gd.nseg) * B;
+        DirectParams iv; // kItem: this unit's view of the launch
+        int ch;
+        int64_t n0;
+        fft_unit_decode<kItem>(p, gd, items, u, B, iv, ch, n0);
+        const DirectParams &pu = kItem ? iv : p;
         double2 park[16]; // the half that is not in LDS: O's stage-1 values, then E's outputs
         double2 *pb = p.park + (size_t)blockIdx.x * kParkSlab * kFftNT + j; // this thread's slab entries
         FFT32_STAMP(0);
@@ -357,7 +365,7 @@ __global__ __launch_bounds__(kFftNT) void fir_fft32_f64_kernel(DirectParams p, c
         __syncthreads();
         FFT32_STAMP(2);
         if (pk_pending >= 0) {
-            if (threadIdx.x == 0) fft_peak_commit(p, pk_pending, pk_lds);
+            if (threadIdx.x == 0) fft_peak_commit(pu, pk_pending, pk_lds);
             pk_pending = -1;
         }
 
@@ -427,8 +435,11 @@ __global__ __launch_bounds__(kFftNT) void fir_fft32_f64_kernel(DirectParams p, c
         {
             const int un1 = fft_unit32(rnd + 1, blockIdx.x, gridDim.x, gd.units);
             const int un = un1 < gd.units ? un1 : u;
-            const int cn = fft_div(un, gd);
-            fft32_stage_samples(p, cn, p.seg0 + (int64_t)(un - cn * gd.nseg) * B, j, flds);
+            DirectParams nv; // kItem: the next unit's view (another row, file or group)
+            int cn;
+            int64_t nn;
+            fft_unit_decode<kItem>(p, gd, items, un, B, nv, cn, nn);
+            fft32_stage_samples(kItem ? nv : p, cn, nn, j, flds);
         }
         FFT32_STAMP(9);
         twiddle16(a, wj); // W_8192^(j c)
@@ -441,9 +452,9 @@ __global__ __launch_bounds__(kFftNT) void fir_fft32_f64_kernel(DirectParams p, c
         // reads: this explicit wait is what stage 1's reads rely on)
         __builtin_amdgcn_s_waitcnt(kVmcnt0);
         FFT32_STAMP(10);
-        const float pk = fft32_store_unit<kOut>(p, ch, n0, B, j, park, a);
+        const float pk = fft32_store_unit<kOut>(pu, ch, n0, B, j, park, a);
         if (ch != pk_ch) {
-            if (p.peak && pk_ch >= 0) {
+            if (pu.peak && pk_ch >= 0) {
                 fft_peak_stage(pk_lds, pk_run);
                 pk_pending = pk_ch;
                 asm volatile("" : "+v"(pk_pending));
@@ -456,7 +467,7 @@ __global__ __launch_bounds__(kFftNT) void fir_fft32_f64_kernel(DirectParams p, c
     }
     // the last unit's restaging transfer must land before the LDS is released
     __builtin_amdgcn_s_waitcnt(kVmcnt0);
-    if (p.peak && pk_ch >= 0) {
+    if (!kItem && p.peak && pk_ch >= 0) { // the item form has no fused peak (items_peak_kernel)
         __syncthreads();
         if (pk_pending >= 0 && threadIdx.x == 0) fft_peak_commit(p, pk_pending, pk_lds);
         __syncthreads();

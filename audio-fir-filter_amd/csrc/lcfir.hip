@@ -98,6 +98,13 @@ struct lcfir_items {
     lcfir::ItemTile *d_row_tiles = nullptr, *d_pcm_tiles = nullptr;
     int64_t n_row_tiles = 0, n_pcm_tiles = 0;
     lcfir::ItemFile *d_files = nullptr;
+    // The fused filter launch's per-unit table (lcfir_items_unit_table), built
+    // at create for the B of the ctx's plan as it was then if that plan's
+    // kernel has an item form (lcfir::fft_items_capable; unit_B = 0: no table),
+    // and the longest row (the chunk rule).
+    lcfir::FftItemUnit *d_units = nullptr;
+    int64_t n_units = 0, unit_B = 0, max_n = 0;
+    std::atomic<int> fusion{LCFIR_ITEMS_FUSION_GROUPS};
     // The codec calls' per-call table (payload offset and format per file):
     // filled into a page-locked slot, copied to d_pcm in stream order.  A slot
     // is rewritten only once the copy that read it is done (its event).
@@ -1460,6 +1467,7 @@ struct ItemsPlan {
     std::vector<int64_t> off, stride;        // per file
     std::vector<int64_t> g_n, g_first, g_rows; // per group
     std::vector<lcfir_items::Launch> launches;
+    std::vector<int32_t> order; // the files with rows, in arena order
     int64_t rows = 0, arena = 0;
 };
 
@@ -1472,7 +1480,7 @@ static int items_plan(int64_t unit, int32_t nfiles, const int64_t *n, const int3
     pl.group.assign((size_t)nfiles, -1);
     pl.off.assign((size_t)nfiles, 0);
     pl.stride.assign((size_t)nfiles, 0);
-    std::vector<int32_t> order;
+    std::vector<int32_t> &order = pl.order;
     for (int32_t f = 0; f < nfiles; ++f) {
         if (n[f] < 0 || nch[f] < 0)
             return fail(LCFIR_EINVAL, "file %d: negative size (n=%lld, nch=%d)", f, (long long)n[f], nch[f]);
@@ -1546,6 +1554,49 @@ int lcfir_items_plan(int64_t unit, int32_t nfiles, const int64_t *n, const int32
     return LCFIR_OK;
 }
 
+// The per-unit table of lcfir_items_unit_table (include/lcfir.h) over a plan
+// made with unit = B: rows in arena order, segments ascending within a row.
+static_assert(sizeof(lcfir_item_unit) == sizeof(lcfir::FftItemUnit) &&
+                  offsetof(lcfir_item_unit, seg) == offsetof(lcfir::FftItemUnit, seg) &&
+                  offsetof(lcfir_item_unit, n) == offsetof(lcfir::FftItemUnit, n),
+              "the ABI's entry is the kernels' entry");
+static int items_unit_count(int64_t B, const int64_t *n, const int32_t *nch, const ItemsPlan &pl, int64_t &total) {
+    total = 0;
+    for (const int32_t f : pl.order) {
+        if (n[f] > INT32_MAX) return fail(LCFIR_EINVAL, "file %d: %lld frames do not fit a unit entry", f, (long long)n[f]);
+        int64_t u = 0;
+        if (__builtin_mul_overflow((n[f] + B - 1) / B, (int64_t)nch[f], &u) || __builtin_add_overflow(total, u, &total))
+            return fail(LCFIR_EINVAL, "the unit count does not fit 63 bits");
+    }
+    return LCFIR_OK;
+}
+static void items_unit_fill(int64_t B, const int64_t *n, const int32_t *nch, const ItemsPlan &pl,
+                            lcfir::FftItemUnit *out) {
+    for (const int32_t f : pl.order)
+        for (int32_t c = 0; c < nch[f]; ++c) {
+            const int64_t off = pl.off[(size_t)f] + c * pl.stride[(size_t)f];
+            const int32_t nseg = (int32_t)((n[f] + B - 1) / B);
+            for (int32_t sg = 0; sg < nseg; ++sg) *out++ = lcfir::FftItemUnit{off, sg, (int32_t)n[f]};
+        }
+}
+
+int lcfir_items_unit_table(int64_t B, int32_t nfiles, const int64_t *n, const int32_t *nch, int64_t *nunits,
+                           lcfir_item_unit *entries, int64_t cap) {
+    if (!nunits) return fail(LCFIR_EINVAL, "nunits is null");
+    *nunits = 0;
+    ItemsPlan pl;
+    int rc = items_plan(B, nfiles, n, nch, pl);
+    if (rc) return rc;
+    int64_t total = 0;
+    rc = items_unit_count(B, n, nch, pl, total);
+    if (rc) return rc;
+    *nunits = total;
+    if (cap < total) return fail(LCFIR_EINVAL, "%lld entries do not fit cap = %lld", (long long)total, (long long)cap);
+    if (total > 0 && !entries) return fail(LCFIR_EINVAL, "entries is null");
+    items_unit_fill(B, n, nch, pl, reinterpret_cast<lcfir::FftItemUnit *>(entries));
+    return LCFIR_OK;
+}
+
 static void items_note_stream(lcfir_items *it, hipStream_t s) {
     std::lock_guard<std::mutex> lk(it->mu);
     for (hipStream_t u : it->used)
@@ -1576,14 +1627,28 @@ int lcfir_items_create(lcfir_ctx *ctx, const int64_t *n, const int32_t *nch, int
     DeviceGuard g(ctx->device);
     if (!g.ok) return fail(LCFIR_EDEVICE, "hipSetDevice(%d) failed", ctx->device);
     int64_t unit = kDirR * kDirNT; // the direct kernel's tile of outputs
+    int64_t unit_B = 0;            // the fused launch's table: plans whose kernel has an item form
     if (resolve_method(ctx) == LCFIR_METHOD_FFT) {
         const int rc = ensure_fft(ctx);
         if (rc) return rc;
         unit = ctx->fft.B;
+        if (lcfir::fft_items_capable(ctx->fft)) unit_B = unit;
     }
     ItemsPlan pl;
     int rc = items_plan(unit, nfiles, n, nch, pl);
     if (rc) return rc;
+    std::vector<lcfir::FftItemUnit> units;
+    int64_t max_n = 0;
+    for (const int32_t f : pl.order) max_n = std::max(max_n, n[f]);
+    if (unit_B > 0 && max_n <= INT32_MAX) {
+        int64_t total = 0;
+        rc = items_unit_count(unit_B, n, nch, pl, total);
+        if (rc) return rc;
+        units.resize((size_t)total);
+        items_unit_fill(unit_B, n, nch, pl, units.data());
+    } else {
+        unit_B = 0; // a row too long for an entry: the per-group path only
+    }
     // the passes' tile tables (items.hpp): fixed-size pieces of every row / of
     // every file's interleaved samples
     std::vector<lcfir::ItemTile> row_tiles, pcm_tiles;
@@ -1614,6 +1679,9 @@ int lcfir_items_create(lcfir_ctx *ctx, const int64_t *n, const int32_t *nch, int
     it->arena = pl.arena;
     it->n_row_tiles = (int64_t)row_tiles.size();
     it->n_pcm_tiles = (int64_t)pcm_tiles.size();
+    it->n_units = (int64_t)units.size();
+    it->unit_B = unit_B;
+    it->max_n = max_n;
     // Plain hipMalloc, not the stream-ordered pool the ctx's tables and scratch
     // recycle: the arenas are large, live as long as the batch and are handed
     // to the caller, and creating an item set is no hot path.
@@ -1635,6 +1703,9 @@ int lcfir_items_create(lcfir_ctx *ctx, const int64_t *n, const int32_t *nch, int
         if (!r)
             r = items_upload(reinterpret_cast<void **>(&it->d_files), files.data(),
                              files.size() * sizeof(lcfir::ItemFile), up);
+        if (!r)
+            r = items_upload(reinterpret_cast<void **>(&it->d_units), units.data(),
+                             units.size() * sizeof(lcfir::FftItemUnit), up);
         if (r) return r;
         if (nfiles > 0) {
             const size_t tb = sizeof(lcfir::ItemPcm) * (size_t)nfiles;
@@ -1668,7 +1739,7 @@ int lcfir_items_destroy(lcfir_items *it) {
     if (!it) return LCFIR_OK;
     DeviceGuard g(it->device);
     for (hipStream_t s : it->used) (void)hipStreamSynchronize(s);
-    void *bufs[] = {it->d_in, it->d_out, it->d_row_tiles, it->d_pcm_tiles, it->d_files, it->d_pcm};
+    void *bufs[] = {it->d_in, it->d_out, it->d_row_tiles, it->d_pcm_tiles, it->d_files, it->d_pcm, it->d_units};
     for (void *p : bufs)
         if (p) (void)hipFree(p);
     for (int k = 0; k < lcfir_items::kPcmSlots; ++k) {
@@ -1699,13 +1770,92 @@ int lcfir_items_info(const lcfir_items *it, int32_t *groups, int32_t *launches, 
     return LCFIR_OK;
 }
 
+int lcfir_items_set_fusion(lcfir_items *it, int mode) {
+    if (!it) return fail(LCFIR_EINVAL, "items is null");
+    if (mode != LCFIR_ITEMS_FUSION_AUTO && mode != LCFIR_ITEMS_FUSION_GROUPS)
+        return fail(LCFIR_EINVAL, "unknown fusion mode %d", mode);
+    it->fusion = mode;
+    return LCFIR_OK;
+}
+
+// The fused path's rule (include/lcfir.h, lcfir_items_filter_dev): fusion on,
+// the ctx's current plan FFT with one partition on a kernel with an item form
+// and the table's B, every row at most one launch chunk long.  Builds the plan if the ctx has none yet.
+static int items_fused(lcfir_items *it, bool &fused) {
+    fused = false;
+    if (it->fusion != LCFIR_ITEMS_FUSION_AUTO || it->unit_B == 0 || it->n_units == 0) return LCFIR_OK;
+    if (resolve_method(it->ctx) != LCFIR_METHOD_FFT) return LCFIR_OK;
+    const int rc = ensure_fft(it->ctx);
+    if (rc) return rc;
+    const lcfir::FftPlan &plan = it->ctx->fft;
+    fused = lcfir::fft_items_capable(plan) && plan.B == it->unit_B && it->max_n <= lcfir::fft_chunk_span(plan);
+    return LCFIR_OK;
+}
+
+int lcfir_items_filter_launches(lcfir_items *it, int32_t *filter_launches, int64_t *fused_units) {
+    if (!it || !filter_launches || !fused_units) return fail(LCFIR_EINVAL, "null argument");
+    DeviceGuard g(it->device);
+    if (!g.ok) return fail(LCFIR_EDEVICE, "hipSetDevice(%d) failed", it->device);
+    bool fused = false;
+    const int rc = items_fused(it, fused);
+    if (rc) return rc;
+    if (fused) {
+        const int64_t per = lcfir::fft_max_units(it->ctx->fft);
+        *filter_launches = (int32_t)std::min<int64_t>((it->n_units + per - 1) / per, INT32_MAX);
+        *fused_units = it->n_units;
+    } else {
+        *filter_launches = (int32_t)it->launches.size();
+        *fused_units = 0;
+    }
+    return LCFIR_OK;
+}
+
+// One launch for all groups: the item form of the plan's kernel over the
+// per-unit table (lcfir::fft_launch_items).  Stream bookkeeping as run_filter.
+static int items_filter_fused(lcfir_items *it, hipStream_t s) {
+    lcfir_ctx *ctx = it->ctx;
+    note_stream(ctx, s);
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs == hipStreamCaptureStatusActive) {
+        std::lock_guard<std::mutex> lk(ctx->fft_mu);
+        ctx->plan_captured = true;
+    }
+    lcfir::DirectParams p{};
+    p.x = it->d_in;
+    p.y = it->d_out;
+    p.taps = ctx->d_taps;
+    p.ntaps = ctx->ntaps;
+    p.half = ctx->half;
+    p.peak_stride = 1;
+    const size_t npark = lcfir::fft32_park_doubles(ctx->fft);
+    if (npark > 0) {
+        bool capture_error = false;
+        double *base = stream_scratch(ctx, s, npark, capture_error);
+        if (capture_error)
+            return fail(LCFIR_EINVAL, "FFT scratch of %zu doubles is not allocated on this stream: run "
+                        "an eager call of this shape on it before HIP graph capture", npark);
+        if (!base) return fail(LCFIR_ENOMEM, "FFT scratch of %zu doubles", npark);
+        p.park = reinterpret_cast<double2 *>(base);
+    }
+    std::string err;
+    if (!lcfir::fft_launch_items(ctx->fft, p, it->d_units, it->n_units, s, err))
+        return fail(LCFIR_EDEVICE, "fft item launch: %s", err.c_str());
+    return LCFIR_OK;
+}
+
 int lcfir_items_filter_dev(lcfir_items *it, float *d_peak, void *stream) {
     if (!it) return fail(LCFIR_EINVAL, "items is null");
     DeviceGuard g(it->device);
     if (!g.ok) return fail(LCFIR_EDEVICE, "hipSetDevice(%d) failed", it->device);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     items_note_stream(it, s);
-    for (const lcfir_items::Launch &l : it->launches) {
+    bool fused = false;
+    int frc = items_fused(it, fused);
+    if (!frc && fused) frc = items_filter_fused(it, s);
+    if (frc) return frc;
+    // the per-group path: one multi-channel launch per group launch
+    for (size_t li = 0; !fused && li < it->launches.size(); ++li) {
+        const lcfir_items::Launch &l = it->launches[li];
         lcfir::DirectParams p{};
         p.x = it->d_in + l.off;
         p.x_lo = 0;

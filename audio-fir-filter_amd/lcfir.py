@@ -115,6 +115,9 @@ _SIGNATURES = {
     "lcfir_items_info": ([_vp, ctypes.POINTER(_c_i32), ctypes.POINTER(_c_i32), ctypes.POINTER(_c_i64),
                           ctypes.POINTER(_c_i64)], _c_int),
     "lcfir_items_filter_dev": ([_vp, _vp, _vp], _c_int),
+    "lcfir_items_unit_table": ([_c_i64, _c_i32, _vp, _vp, ctypes.POINTER(_c_i64), _vp, _c_i64], _c_int),
+    "lcfir_items_set_fusion": ([_vp, _c_int], _c_int),
+    "lcfir_items_filter_launches": ([_vp, ctypes.POINTER(_c_i32), ctypes.POINTER(_c_i64)], _c_int),
     "lcfir_items_normalize_dev": ([_vp, _vp, _c_int, _vp], _c_int),
     "lcfir_items_decode_pcm_dev": ([_vp, _vp, _vp, _vp, _vp], _c_int),
     "lcfir_items_encode_pcm_scaled_dev": ([_vp, _vp, _c_int, _vp, _vp, _vp, _vp], _c_int),
@@ -357,10 +360,17 @@ Filter.filter_window_dev = _filter_window_dev
 Filter.filter_window_norm_dev = _filter_window_norm_dev
 
 
+ITEMS_FUSION = {"auto": 0, "groups": 1}
+# lcfir_item_unit: one (row, segment) of the fused filter launch's table
+ITEM_UNIT = np.dtype([("off", np.int64), ("seg", np.int32), ("n", np.int32)])
+
+
 class ItemSet:
     """lcfir_items_*: a batch of files of different lengths (the reference's
     batch scenario, main.cp:132-147) laid out as zero-padded rows of one arena
-    and filtered in one launch per group of equal unit count, with ragged
+    and filtered in one launch per group of equal unit count (the default) or
+    one for all groups (set_fusion("auto"): the per-unit table; single-partition
+    FFT plans on the LDS-column kernels), with ragged
     peak / normalize / codec passes of one launch each.  `nframes[f]` frames
     and `nch[f]` channels per file.  Serves one stream at a time."""
 
@@ -399,6 +409,41 @@ class ItemSet:
         return {"file_group": fg, "file_offset": fo, "file_stride": fs, "group_n": gn[:g].copy(),
                 "group_first_row": gf[:g].copy(), "group_rows": gr[:g].copy(), "groups": g,
                 "launches": nl.value, "rows": rows.value, "arena_floats": arena.value}
+
+    @staticmethod
+    def unit_table(B: int, nframes, nch, cap=None) -> np.ndarray:
+        """lcfir_items_unit_table, a pure function (no device): the fused
+        launch's table as an ITEM_UNIT array, one entry per (row, segment) in
+        arena order.  cap: the capacity passed to the library (default: the
+        total, asked for first); a smaller one raises LcfirError."""
+        n = np.ascontiguousarray(np.asarray(nframes, dtype=np.int64).reshape(-1))
+        c = np.ascontiguousarray(np.asarray(nch, dtype=np.int32).reshape(-1))
+        if n.size != c.size:
+            raise ValueError("nframes and nch differ in length")
+        lib, total = load(), ctypes.c_int64()
+        if cap is None:
+            rc = lib.lcfir_items_unit_table(int(B), int(n.size), n.ctypes.data, c.ctypes.data, ctypes.byref(total),
+                                            None, 0)
+            if total.value > 0:
+                rc = 0  # the total only: cap = 0 is too small by design
+            _check(rc)
+            cap = total.value
+        out = np.zeros(int(cap), ITEM_UNIT)
+        _check(lib.lcfir_items_unit_table(int(B), int(n.size), n.ctypes.data, c.ctypes.data, ctypes.byref(total),
+                                          out.ctypes.data, int(cap)))
+        return out[:total.value]
+
+    def set_fusion(self, mode):
+        """"groups" (the default): the per-group launches; "auto": one filter
+        launch for all groups where the plan allows."""
+        _check(load().lcfir_items_set_fusion(self._h, ITEMS_FUSION[mode] if isinstance(mode, str) else int(mode)))
+
+    def filter_launches(self):
+        """(filter launches, fused units) of the next filter_dev under the
+        ctx's current plan; fused units = 0 on the per-group path."""
+        nl, nu = ctypes.c_int32(), ctypes.c_int64()
+        _check(load().lcfir_items_filter_launches(self._h, ctypes.byref(nl), ctypes.byref(nu)))
+        return nl.value, nu.value
 
     def file(self, f: int):
         """(d_x, d_y, stride): file f's rows in the input and output arenas as

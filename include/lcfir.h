@@ -389,12 +389,34 @@ int lcfir_items_plan(int64_t unit, int32_t nfiles, const int64_t *n, const int32
                      int32_t *ngroups, int64_t *group_n, int64_t *group_first_row, int64_t *group_rows,
                      int32_t *nlaunches, int64_t *nrows, int64_t *arena_floats);
 
+/* The per-unit table of an item set: one entry per (row, segment) of every
+ * file with rows, rows in arena order (lcfir_items_plan's), segments ascending
+ * within a row.  Entry: the row's arena offset in floats (the file's offset +
+ * channel * stride), the segment (outputs [seg B, min((seg + 1) B, n)) of the
+ * row) and the FILE's frame count n, not the group's N_g.  A row of n frames
+ * has ceil(n / B) entries, so the total is sum nch ceil(n / B).  A pure
+ * function (no device).  *nunits always receives the total; entries (nullable
+ * when cap = 0) is written only if cap >= the total, else nothing is written
+ * and the call returns LCFIR_EINVAL.  n[f] > 2^31 - 1 on a file with rows is
+ * LCFIR_EINVAL (the entry holds n in 32 bits). */
+typedef struct lcfir_item_unit {
+    int64_t off;
+    int32_t seg;
+    int32_t n;
+} lcfir_item_unit;
+int lcfir_items_unit_table(int64_t B, int32_t nfiles, const int64_t *n, const int32_t *nch, int64_t *nunits,
+                           lcfir_item_unit *entries, int64_t cap);
+
 typedef struct lcfir_items lcfir_items;
 /* Plans nfiles files (n[f] frames, nch[f] channels) with unit = the outputs
  * per work unit of the ctx's method as resolved now (lcfir_ctx_fft_units'
  * *outputs for the FFT method, 4 096 for the direct form), allocates an input
  * and an output arena of the planned length on the ctx's device, zeroes the
- * input arena once and uploads the tile tables the passes below walk.  The
+ * input arena once and uploads the tile tables the passes below walk.  If the
+ * ctx's plan is then a single-partition FFT plan on an LDS-column kernel
+ * (LCFIR_FFT_KERNEL_L16 or _L32_PARK), the per-unit table
+ * (lcfir_items_unit_table at that plan's outputs per unit) is uploaded too and
+ * its B recorded: what the fused filter launch below walks.  The
  * ctx must outlive the item set's lcfir_items_filter_dev calls.  An item set
  * serves one stream at a time: calls on one stream run in order; the caller
  * orders a change of stream itself. */
@@ -410,14 +432,42 @@ int lcfir_items_destroy(lcfir_items *items);
 int lcfir_items_file(const lcfir_items *items, int32_t f, float **d_x, float **d_y, int64_t *stride);
 int lcfir_items_info(const lcfir_items *items, int32_t *groups, int32_t *launches, int64_t *rows,
                      int64_t *arena_floats);
-/* Filters every file: one multi-channel launch per group launch (x_hi = end
- * = N_g, no fused peak), then, if d_peak is non-NULL, one launch that max-es
+/* Filters every file, then, if d_peak is non-NULL, one launch that max-es
  * each file's max|y| over its channels and over [0, n_f) only into
  * d_peak[f] (nfiles floats, zeroed by the caller as for
- * lcfir_filter_channels_dev; NaN skipped, Inf taken).  Allocates nothing
+ * lcfir_filter_channels_dev; NaN skipped, Inf taken).
+ * Per-group path (the default): one ordinary multi-channel launch per group
+ * launch (x_hi = end = N_g, no fused peak); outputs [n, N_g) of a shorter row
+ * then hold the ringing tail.
+ * Fused path (lcfir_items_set_fusion): ONE filter launch for all groups, the
+ * item form of the plan's FFT kernel walking the per-unit table: every unit
+ * runs with exactly the parameters the per-file call gives it (x_hi = end =
+ * the file's n), so outputs [0, n) are lcfir_filter_channels_dev's bytes and
+ * nothing of a row past n is written.  Taken when fusion is
+ * LCFIR_ITEMS_FUSION_AUTO, the ctx's current plan is FFT with one partition on
+ * an LDS-column kernel (LCFIR_FFT_KERNEL_L16 or _L32_PARK; the register kernel
+ * has no item form) with the table's B, and every row is at most one launch
+ * chunk long (the `chunk` tuning; 2^28 outputs by default); a max_units
+ * tuning splits it into consecutive launches of that many entries.  Otherwise
+ * (the direct method, a partitioned plan, a register-kernel plan, a seg_len
+ * changed after create, a row longer than a chunk) the per-group path.  Both
+ * paths give the same bytes in [0, n) of every row.  Allocates nothing
  * beyond what the filter launches do, so it captures into a HIP graph under
  * their rule (an eager call on the stream first sizes the FFT scratch). */
 int lcfir_items_filter_dev(lcfir_items *items, float *d_peak, void *stream);
+/* How lcfir_items_filter_dev picks its path: GROUPS (the default: the fused
+ * launch's step time is not measured yet) always runs the
+ * per-group launches, AUTO fuses where the rule above allows. */
+#define LCFIR_ITEMS_FUSION_AUTO 0
+#define LCFIR_ITEMS_FUSION_GROUPS 1
+int lcfir_items_set_fusion(lcfir_items *items, int mode);
+/* What the next lcfir_items_filter_dev would launch under the ctx's plan as it
+ * is now: the fused path's launches (1 unless a max_units tuning splits the
+ * table) and the table entries they run; on the per-group path
+ * lcfir_items_info's launches (the plan's group launches; each still runs one
+ * kernel per chunk and partition) and 0 entries.  The peak launch is not
+ * counted. */
+int lcfir_items_filter_launches(lcfir_items *items, int32_t *filter_launches, int64_t *fused_units);
 /* One launch: file f's output rows [0, n_f) become
  * (float)((double)y * (1.0 / (double)d_peak[f])) iff (d_peak[f] > 1 or
  * force) and d_peak[f] > 0 -- lcfir_normalize_dev per file with npeak = 1

@@ -1,13 +1,20 @@
 #!/usr/bin/env python3
-"""Rate of a batch of short files three ways, on one device in one process:
+"""Rate of a batch of short files four ways, on one device in one process:
 
   (a) eager    per-file lcfir_filter_window_dev calls on one stream
                (batch.BatchRunner, one lane: fused peak, the normalize riding
                in the next file's launch);
   (b) graphed  the same steps on ten lanes replayed from a HIP graph, as
                `bench.py --config 1` arranges them (batch.GraphedSteps);
-  (c) items    one item set (batch.ItemBatch): one filter launch per group of
-               equal unit count, one ragged peak launch, one ragged normalize.
+  (c) items    one item set (batch.ItemBatch, fusion="auto"): one filter
+               launch for all groups over the per-unit table where the plan's
+               kernel has an item form (the L = 16 384 and the park kernel; a
+               register-kernel plan, as 19 201 linear-phase taps give by
+               default, stays on the per-group launches: see "filter_launches"
+               in the output, and --family lds), one ragged peak launch, one
+               ragged normalize;
+  (d) items_groups  a second item set with fusion="groups": one filter launch
+               per group of equal unit count, then the same two ragged passes.
 
 A step is filter + per-file peak + the per-file normalize decision for every
 file of the batch.  Workloads: BASELINE config 1's shape repeated (--files
@@ -17,8 +24,8 @@ the device pre-rolled, then the arrangements are timed in alternation
 (--rounds windows each, HIP events around --steps steps on the stream that
 runs them, and a host clock that stops after a device synchronise beside
 them); the rate is the batch's samples x steps / the window's event time.
-Before and after timing, (c)'s outputs and peaks are compared with (a)'s bit
-for bit.
+Before and after timing, (c)'s and (d)'s outputs and peaks are compared with
+(a)'s bit for bit.
 Prints a table and one JSON line; not part of bench.py.
 """
 import argparse
@@ -42,8 +49,10 @@ def build(torch, lcfir, batch, flt, files, dev, lanes):
     run_b = batch.BatchRunner(be_b, 0, 1, nframes, 1, half, False, "file", lanes=lanes)
     run_b.prepare(lambda f, lo, hi: files[f][:, lo:hi])
     ibe = batch.DeviceItemBackend(flt, dev)
-    ib = batch.ItemBatch(ibe, files)
-    return be_a, run_a, be_b, run_b, ibe, ib
+    ib = batch.ItemBatch(ibe, files, fusion="auto")
+    ibe_g = batch.DeviceItemBackend(flt, dev)
+    ib_g = batch.ItemBatch(ibe_g, files, fusion="groups")
+    return be_a, run_a, be_b, run_b, ibe, ib, ibe_g, ib_g
 
 
 def window(torch, stream, fn, calls):
@@ -66,17 +75,31 @@ def window(torch, stream, fn, calls):
 
 def measure(args, torch, lcfir, batch, np, name, files, taps, dev):
     flt = lcfir.Filter(taps, device=dev.index or 0, method="auto")
-    be_a, run_a, be_b, run_b, ibe, ib = build(torch, lcfir, batch, flt, files, dev, args.lanes)
+    if args.family != "default":
+        flt.set_fft_family(args.family)
+    be_a, run_a, be_b, run_b, ibe, ib, ibe_g, ib_g = build(torch, lcfir, batch, flt, files, dev, args.lanes)
     samples = sum(f.size for f in files)
-    # same bytes first: the item set against the per-file calls
-    run_a.step()
-    ib.step()
-    torch.cuda.synchronize()
-    want = {sh.file: y.cpu().numpy() for sh, y in run_a.results()}
-    pk_a, pk_c = run_a.peaks.cpu().numpy()[:len(files)], ib.peaks.cpu().numpy()[:len(files)]
-    same = bool(np.array_equal(pk_a.view(np.uint32), pk_c.view(np.uint32)))
-    for f, y in enumerate(ib.results()):
-        same = same and bool(np.array_equal(y.cpu().numpy().view(np.uint32), want[f].view(np.uint32)))
+    sets = {"items": ib, "items_groups": ib_g}
+    launched = {k: v.b.items.filter_launches() for k, v in sets.items()}
+
+    def same_as_eager():
+        """both item sets against the per-file calls, outputs and peaks"""
+        run_a.step()
+        for v in sets.values():
+            v.step()
+        torch.cuda.synchronize()
+        want = {sh.file: y.cpu().numpy() for sh, y in run_a.results()}
+        pk_a = run_a.peaks.cpu().numpy()[:len(files)]
+        ok = {}
+        for k, v in sets.items():
+            pk_c = v.peaks.cpu().numpy()[:len(files)]
+            ok[k] = bool(np.array_equal(pk_a.view(np.uint32), pk_c.view(np.uint32)))
+            for f, y in enumerate(v.results()):
+                ok[k] = ok[k] and bool(np.array_equal(y.cpu().numpy().view(np.uint32), want[f].view(np.uint32)))
+        return ok
+
+    # same bytes first
+    same = same_as_eager()
     for _ in range(3):
         run_b.step()
     graphed = batch.GraphedSteps(run_b, be_b)
@@ -89,6 +112,7 @@ def measure(args, torch, lcfir, batch, np, name, files, taps, dev):
         "eager": (s_a, run_a.step, args.steps, args.steps),
         "graphed": (be_b.streams[0], graphed.replay, replays, replays * per_replay),
         "items": (s_a, ib.step, args.steps, args.steps),
+        "items_groups": (s_a, ib_g.step, args.steps, args.steps),
     }
     # pre-roll: untimed work until the clock has settled, every arrangement warm
     t0 = time.perf_counter()
@@ -104,15 +128,15 @@ def measure(args, torch, lcfir, batch, np, name, files, taps, dev):
             host[k].append(wall / steps)
     # the timed steps computed what the first ones did
     with torch.cuda.stream(s_a):
-        run_a.step()
-        ib.step()
-    torch.cuda.synchronize()
-    want = {sh.file: y.cpu().numpy() for sh, y in run_a.results()}
-    for f, y in enumerate(ib.results()):
-        same = same and bool(np.array_equal(y.cpu().numpy().view(np.uint32), want[f].view(np.uint32)))
+        again = same_as_eager()
+    same = {k: same[k] and again[k] for k in same}
+    cus = int(torch.cuda.get_device_properties(dev).multi_processor_count)
     out = {"workload": name, "files": len(files), "samples_per_step": samples, "ntaps": int(flt.ntaps),
-           "fft": flt.fft_info, "unit": flt.fft_units["outputs"], "groups": ib.layout["groups"],
-           "launches": ib.layout["launches"], "items_equal_per_file_calls": same, "rounds": args.rounds,
+           "fft": flt.fft_info, "unit": flt.fft_units["outputs"], "kernel": flt.fft_units["kernel"], "groups": ib.layout["groups"],
+           "launches": ib.layout["launches"], "items_equal_per_file_calls": all(same.values()),
+           "equal_per_file_calls": same, "filter_launches": {k: v[0] for k, v in launched.items()},
+           "fused_units": launched["items"][1], "cus": cus, "grid_rounds": -(-launched["items"][1] // cus),
+           "rounds": args.rounds,
            "steps_per_window": {k: v[3] for k, v in arrangements.items()}}
     for k, v in ms.items():
         med = statistics.median(v)
@@ -123,6 +147,7 @@ def measure(args, torch, lcfir, batch, np, name, files, taps, dev):
     run_b.close()
     torch.cuda.synchronize()
     ibe.close()
+    ibe_g.close()
     flt.close()
     return out
 
@@ -136,6 +161,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=5, help="timed windows per arrangement, alternating")
     ap.add_argument("--lanes", type=int, default=10)
     ap.add_argument("--preroll-s", type=float, default=1.0)
+    ap.add_argument("--family", choices=["default", "lds"], default="default",
+                    help="lcfir_ctx_set_fft_family: lds runs the LDS-column kernels, which have the item form")
     ap.add_argument("--seed", type=int, default=20260206)
     ap.add_argument("--out", default=None, help="also write the JSON here")
     args = ap.parse_args()
@@ -162,10 +189,12 @@ def main():
         r = measure(args, torch, lcfir, batch, np, name, files, taps, dev)
         results.append(r)
         print(f"{name}: {r['files']} files, {r['samples_per_step']} samples/step, {r['ntaps']} taps, "
-              f"unit {r['unit']}, {r['groups']} groups, same bytes: {r['items_equal_per_file_calls']}")
-        for k in ("eager", "graphed", "items"):
+              f"unit {r['unit']} ({r['kernel']}), {r['groups']} groups, filter launches {r['filter_launches']}, "
+              f"{r['fused_units']} fused units = {r['grid_rounds']} rounds of {r['cus']} CUs, "
+              f"same bytes: {r['equal_per_file_calls']}")
+        for k in ("eager", "graphed", "items", "items_groups"):
             v = r[k]
-            print(f"  {k:8s} {v['step_ms_median']:9.4f} ms/step (min {v['step_ms_min']:.4f}, max "
+            print(f"  {k:12s} {v['step_ms_median']:9.4f} ms/step (min {v['step_ms_min']:.4f}, max "
                   f"{v['step_ms_max']:.4f}; host clock {v['host_step_ms_median']:.4f})  "
                   f"{v['gsamples_per_s']:8.3f} Gsamples/s")
     line = json.dumps({"items_rate": results})
