@@ -534,8 +534,11 @@ class ItemBackend:
         raise NotImplementedError
 
     def set_fusion(self, mode: str):
-        """"auto" / "groups" (lcfir.ItemSet.set_fusion): how the filter step is
-        launched, never what it computes.  A backend without launches ignores it."""
+        """"auto" / "groups" / "parts" (lcfir.ItemSet.set_fusion): how the filter
+        step is launched, never what it computes: per group ("groups"), one
+        launch for all groups of a single-partition plan ("auto"), or that and
+        one launch per partition for all groups of a partitioned plan ("parts").
+        A backend without launches ignores it."""
 
     def load(self, arena):
         """the whole input arena ([arena_floats] float32, host) in one copy"""
@@ -564,7 +567,8 @@ class ItemBatch:
     """A batch of files of different lengths and channel counts through one
     item set (lcfir.ItemSet): one upload of the whole arena, then per step one
     filter launch per group of equal unit count (fusion="groups", the default)
-    or one for all groups (fusion="auto", where the plan allows), one ragged
+    or one for all groups (fusion="auto", where the plan allows; fusion="parts"
+    also fuses a partitioned plan, one launch per partition), one ragged
     peak launch and one ragged normalize launch, whatever the number of files.  The per-file
     results are what BatchRunner gives for the same files, bit for bit
     (ProcessFile.cp:91-101 per file: rescale iff peak > 1 or `normalize`).
@@ -573,8 +577,8 @@ class ItemBatch:
 
     def __init__(self, backend: ItemBackend, files: Sequence, normalize: bool = False, fusion: str = "groups"):
         import numpy as np
-        if fusion not in ("auto", "groups"):
-            raise ValueError(f"fusion must be 'auto' or 'groups', got {fusion!r}")
+        if fusion not in ("auto", "groups", "parts"):
+            raise ValueError(f"fusion must be 'auto', 'groups' or 'parts', got {fusion!r}")
         self.b = backend
         self.normalize = normalize
         self.fusion = fusion

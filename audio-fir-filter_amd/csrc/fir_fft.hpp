@@ -306,7 +306,7 @@ __host__ __device__ inline int fft_div(int u, const FftGrid &g) {
     return (int)(((uint64_t)(uint32_t)u * g.m) >> g.sh);
 }
 
-// The item form of the single-partition kernels (template flag kItem; item
+// The item form of the LDS-column kernels (template flag kItem; item
 // sets, include/lcfir.h lcfir_items_*): the launch's units are the entries of
 // a device table instead of a (channel, segment) grid, so one launch covers
 // rows of any lengths, from any files and groups of an arena.  (The two
@@ -314,6 +314,24 @@ __host__ __device__ inline int fft_div(int u, const FftGrid &g) {
 // unit u its own view of the launch parameters (fft_unit_decode): exactly the
 // parameters the per-file call gives that unit, so its stores are that call's
 // bytes and nothing of a row past its file's n is written.
+//
+// The partition modes (kFftOutFirst / Add / Last, a filter of plan.parts > 1
+// partitions) have the item form too, behind entry points of their own
+// (fir_fft_items_parts_kernel, fir_fft32_items_parts_kernel), so the two
+// kernels above keep the instances they had: P launches walk the same table, and the
+// f64 partial sums live in an arena-shaped scratch (p.y64: one double per arena
+// float), row by row at the row's own arena offset.  For a file of n <=
+// fft_chunk_span(plan) frames fft_launch_group gives partition `part` of unit
+// (row, seg) exactly these parameters: one chunk, q.start = 0, q.end = n;
+// x_lo = max(0, -half) = 0; x_hi = min(n, whi) = n, since whi >= n (whi =
+// last + B + parts ntaps - 1 - half with n <= last + B and parts ntaps > half);
+// scratch element 0 = output 0; half - part plan.ntaps and plan.ntaps from the
+// launch.  The item view is the same, so every load, partial sum, add and final
+// rounding is the per-file call's: outputs [0, n) are its bytes, and nothing of
+// a row past n is written in the output arena.  In the scratch, kFftOutFirst
+// writes every valid output of [0, n) of every row before Add and Last read it
+// (stream order), and the rows' slices are disjoint, so stale scratch contents
+// -- an earlier call's, another row's, a NaN's -- never reach an output.
 struct FftItemUnit {
     int64_t off; // arena offset of the unit's row, floats
     int32_t seg; // its segment of the row: outputs [seg B, min((seg + 1) B, n))
@@ -329,7 +347,8 @@ typedef const __attribute__((address_space(4))) FftItemUnit *fft_item_ptr;
 // the view is p itself (`view` stays untouched: callers read `kItem ? view : p`).
 // Item form: p with x = arena_in + off, y = arena_out + off, the ranges
 // x_lo = y_lo = start = seg0 = 0, x_hi = end = n, no fused peak; ch = 0,
-// n0 = seg B.
+// n0 = seg B; y64 = the row's own slice of the arena-shaped scratch, element
+// 0 = output 0 of the row (the partition modes; y64_stride unused, ch = 0).
 template <bool kItem>
 __device__ __forceinline__ void fft_unit_decode(const DirectParams &p, const FftGrid &gd, const FftItemUnit *items,
                                                 int u, int B, DirectParams &view, int &ch, int64_t &n0) {
@@ -343,6 +362,7 @@ __device__ __forceinline__ void fft_unit_decode(const DirectParams &p, const Fft
         view = p;
         view.x = p.x + off;
         view.y = p.y + off;
+        view.y64 = p.y64 + off;
         view.x_lo = view.y_lo = view.start = view.seg0 = 0;
         view.x_hi = view.end = n;
         view.peak = nullptr;
@@ -1049,15 +1069,17 @@ __device__ __forceinline__ void fft_columns(double2 *flds, const double2 *twl, c
 //   kFftOutLast  : RNE(p.y64 + partial) to f32 into y, fused peak.
 // c8 = the special lane's bin-M/2 coefficient 2S - 2D of this pair table.
 // kNrm: the launch also rescales a previous file's outputs (FftNrm).
-// kItem: the item form (fft_unit_decode), kFftOutSym and kFftOutF32 without kNrm.
-template <int kOut, bool kNrm = false, bool kItem = false>
-__global__ __launch_bounds__(kFftNT) void fir_fft_f64_kernel(DirectParams p, const double2 *__restrict__ pair,
-                                                            const double2 *__restrict__ tw,
-                                                            const uint32_t *__restrict__ task, int B,
-                                                            FftGrid gd, double2 c8, FftNrm nrm,
-                                                            const FftItemUnit *items) {
-    static_assert(!kItem || (!kNrm && (kOut == kFftOutSym || kOut == kFftOutF32)),
-                  "item form: single-partition filters, no fused normalize");
+// kItem: the item form (fft_unit_decode), every output mode, without kNrm.
+// The body of two entry points: fir_fft_f64_kernel (every plain form, and the
+// item form of the single-partition modes) and fir_fft_items_parts_kernel (the
+// item form of the partition modes), below.
+template <int kOut, bool kNrm, bool kItem>
+__device__ __forceinline__ void fir_fft_f64_body(DirectParams p, const double2 *__restrict__ pair,
+                                                 const double2 *__restrict__ tw,
+                                                 const uint32_t *__restrict__ task, int B,
+                                                 FftGrid gd, double2 c8, FftNrm nrm,
+                                                 const FftItemUnit *items) {
+    static_assert(!kItem || !kNrm, "item form: no fused normalize");
     extern __shared__ double2 flds[];
     FFT_USTAMP(0);
     // kNrm: the normalize decision, once per launch (uniform)
@@ -1334,6 +1356,31 @@ __global__ __launch_bounds__(kFftNT) void fir_fft_f64_kernel(DirectParams p, con
         __syncthreads();
         if (threadIdx.x == 0) fft_peak_commit(p, pk_ch, pk_lds);
     }
+}
+
+// kItem here: the single-partition output modes only (kFftOutSym, kFftOutF32)
+template <int kOut, bool kNrm = false, bool kItem = false>
+__global__ __launch_bounds__(kFftNT) void fir_fft_f64_kernel(DirectParams p, const double2 *__restrict__ pair,
+                                                            const double2 *__restrict__ tw,
+                                                            const uint32_t *__restrict__ task, int B,
+                                                            FftGrid gd, double2 c8, FftNrm nrm,
+                                                            const FftItemUnit *items) {
+    static_assert(!kItem || (!kNrm && (kOut == kFftOutSym || kOut == kFftOutF32)),
+                  "item form: single-partition filters, no fused normalize");
+    fir_fft_f64_body<kOut, kNrm, kItem>(p, pair, tw, task, B, gd, c8, nrm, items);
+}
+// The item form of the partition modes (kFftOutFirst / Add / Last over the
+// per-unit table, FftItemUnit): an entry point of its own, so the instances of
+// fir_fft_f64_kernel stay the set they were.
+template <int kOut>
+__global__ __launch_bounds__(kFftNT) void fir_fft_items_parts_kernel(DirectParams p,
+                                                                    const double2 *__restrict__ pair,
+                                                                    const double2 *__restrict__ tw,
+                                                                    const uint32_t *__restrict__ task, int B,
+                                                                    FftGrid gd, double2 c8,
+                                                                    const FftItemUnit *items) {
+    static_assert(kOut == kFftOutFirst || kOut == kFftOutAdd || kOut == kFftOutLast, "the partition modes");
+    fir_fft_f64_body<kOut, false, true>(p, pair, tw, task, B, gd, c8, FftNrm{}, items);
 }
 
 #include "fir_fft32.hpp"
@@ -1903,22 +1950,42 @@ inline bool fft_launch_group(const FftPlan &plan, const DirectParams &p, int nch
 
 // The item form (fft_unit_decode): can the plan's kernel run units from a table?
 // Single-partition plans on the LDS-column kernels (fir_fft_f64_kernel,
-// fir_fft32_f64_kernel): the partition modes, the fused normalize and the
-// register kernel (fir_fft32r_kernel) have no item instantiation.
+// fir_fft32_f64_kernel): the fused normalize and the register kernel
+// (fir_fft32r_kernel) have no item instantiation.  (The rule of
+// LCFIR_ITEMS_FUSION_AUTO; partitioned plans: fft_items_parts_capable.)
 inline bool fft_items_capable(const FftPlan &plan) { return plan.ready && plan.parts == 1 && !plan.reg32; }
+// The same kernels' partition modes over the table: P launches, First, Add ...
+// Add, Last (LCFIR_ITEMS_FUSION_PARTS).  parts > 1 never selects the register
+// kernel (fft_reg32 needs one partition); !reg32 states it.
+inline bool fft_items_parts_capable(const FftPlan &plan) { return plan.ready && !plan.reg32 && plan.parts > 1; }
 
-// one item-form launch: the kernel's usual LDS size and attribute, grid = min(units, CUs)
+// one item-form launch: the kernel's usual LDS size and attribute, grid = min(units, CUs);
+// pair: the partition's pair table(s)
 template <auto kKernel, class C8, class... Tail>
-inline void fft_items_launch_kernel(size_t lds, const FftPlan &plan, const DirectParams &q, const FftItemUnit *items,
-                                    int64_t units, hipStream_t s, C8 c8, Tail... tail) {
+inline void fft_items_launch_kernel(size_t lds, const FftPlan &plan, const DirectParams &q, const double2 *pair,
+                                    const FftItemUnit *items, int64_t units, hipStream_t s, C8 c8, Tail... tail) {
     static const bool attr = [lds] {
         return hipFuncSetAttribute(reinterpret_cast<const void *>(kKernel),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
     }();
     (void)attr;
     const int64_t grid = std::min<int64_t>(units, (int64_t)plan.cus);
-    hipLaunchKernelGGL(kKernel, dim3((unsigned)grid), dim3(kFftNT), lds, s, q, plan.d_pair, plan.d_tw, plan.d_task,
+    hipLaunchKernelGGL(kKernel, dim3((unsigned)grid), dim3(kFftNT), lds, s, q, pair, plan.d_tw, plan.d_task,
                        plan.B, fft_grid(1, units) /* the item form reads gd.units only */, c8, tail..., items);
+}
+// partition `part` of a partitioned plan over nu table entries, output mode kOut
+// (the pair table and c8 as fft_launch_one / fft32_launch_one select them)
+template <int kOut>
+inline void fft_items_launch_part(const FftPlan &plan, const DirectParams &q, int part, const FftItemUnit *tb,
+                                  int64_t nu, hipStream_t s) {
+    if (plan.L == kFft32L)
+        fft_items_launch_kernel<&fir_fft32_items_parts_kernel<kOut>>(fft_lds_bytes(kFft32L), plan, q,
+                                                                  plan.d_pair + (size_t)part * 2 * kFftPairTable, tb,
+                                                                  nu, s, plan.c8[(size_t)part]);
+    else
+        fft_items_launch_kernel<&fir_fft_items_parts_kernel<kOut>>(fft_lds_bytes(), plan, q,
+                                                                  plan.d_pair + (size_t)part * kFftPairTable, tb, nu,
+                                                                  s, plan.c8[(size_t)part]);
 }
 // Filter the `units` rows x segments of the device table `items` (arena row
 // order, segments ascending) in launches of at most fft_max_units entries: one
@@ -1926,15 +1993,26 @@ inline void fft_items_launch_kernel(size_t lds, const FftPlan &plan, const Direc
 // stream's slab (L = 32 768 park kernel); every range field comes from the
 // table.  Every row's n is at most fft_chunk_span(plan) (the caller checks), so
 // each unit's view is the per-file call's single chunk.
+// A partitioned plan (fft_items_parts_capable) runs plan.parts launches per
+// slice of the table, First, Add ... Add, Last, each with its partition's pair
+// table, c8 and half - part ntaps; p.y64: one double per arena float (the
+// rows' partial sums at the rows' own offsets, FftItemUnit).  The slices'
+// rows are disjoint in the scratch, so slice-major order gives the bytes of
+// partition-major order.
 inline bool fft_launch_items(const FftPlan &plan, const DirectParams &p, const FftItemUnit *items, int64_t units,
                              hipStream_t s, std::string &err) {
     if (units <= 0) return true;
-    if (!fft_items_capable(plan) || !items) {
+    const bool parts = fft_items_parts_capable(plan);
+    if ((!fft_items_capable(plan) && !parts) || !items) {
         err = "no item form of this plan's kernel";
         return false;
     }
     if (plan.L == kFft32L && !p.park && kParkSlab > 0) {
         err = "L = 32768 launch without its park slab";
+        return false;
+    }
+    if (parts && !p.y64) {
+        err = "partitioned filter without partial-sum scratch";
         return false;
     }
     DirectParams q = p;
@@ -1944,18 +2022,35 @@ inline bool fft_launch_items(const FftPlan &plan, const DirectParams &p, const F
     for (int64_t u0 = 0; u0 < units; u0 += per) {
         const int64_t nu = std::min(per, units - u0);
         const FftItemUnit *tb = items + u0;
+        if (parts) {
+            for (int part = 0; part < plan.parts; ++part) {
+                DirectParams qp = q;
+                qp.half = p.half - part * plan.ntaps; // partition part covers taps [part * ntaps, ...)
+                if (part == 0) fft_items_launch_part<kFftOutFirst>(plan, qp, part, tb, nu, s);
+                else if (part < plan.parts - 1) fft_items_launch_part<kFftOutAdd>(plan, qp, part, tb, nu, s);
+                else fft_items_launch_part<kFftOutLast>(plan, qp, part, tb, nu, s);
+                const hipError_t e = hipGetLastError();
+                if (e != hipSuccess) {
+                    err = hipGetErrorString(e);
+                    return false;
+                }
+            }
+            continue;
+        }
         if (plan.L == kFft32L && plan.sym)
-            fft_items_launch_kernel<&fir_fft32_f64_kernel<kFftOutSym, true>>(fft_lds_bytes(kFft32L), plan, q, tb, nu,
-                                                                            s, plan.c8[0]);
+            fft_items_launch_kernel<&fir_fft32_f64_kernel<kFftOutSym, true>>(fft_lds_bytes(kFft32L), plan, q,
+                                                                            plan.d_pair, tb, nu, s, plan.c8[0]);
         else if (plan.L == kFft32L)
-            fft_items_launch_kernel<&fir_fft32_f64_kernel<kFftOutF32, true>>(fft_lds_bytes(kFft32L), plan, q, tb, nu,
-                                                                            s, plan.c8[0]);
+            fft_items_launch_kernel<&fir_fft32_f64_kernel<kFftOutF32, true>>(fft_lds_bytes(kFft32L), plan, q,
+                                                                            plan.d_pair, tb, nu, s, plan.c8[0]);
         else if (plan.sym)
-            fft_items_launch_kernel<&fir_fft_f64_kernel<kFftOutSym, false, true>>(fft_lds_bytes(), plan, q, tb, nu, s,
-                                                                                 plan.c8[0], FftNrm{});
+            fft_items_launch_kernel<&fir_fft_f64_kernel<kFftOutSym, false, true>>(fft_lds_bytes(), plan, q,
+                                                                                 plan.d_pair, tb, nu, s, plan.c8[0],
+                                                                                 FftNrm{});
         else
-            fft_items_launch_kernel<&fir_fft_f64_kernel<kFftOutF32, false, true>>(fft_lds_bytes(), plan, q, tb, nu, s,
-                                                                                 plan.c8[0], FftNrm{});
+            fft_items_launch_kernel<&fir_fft_f64_kernel<kFftOutF32, false, true>>(fft_lds_bytes(), plan, q,
+                                                                                 plan.d_pair, tb, nu, s, plan.c8[0],
+                                                                                 FftNrm{});
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) {
             err = hipGetErrorString(e);

@@ -100,8 +100,9 @@ struct lcfir_items {
     lcfir::ItemFile *d_files = nullptr;
     // The fused filter launch's per-unit table (lcfir_items_unit_table), built
     // at create for the B of the ctx's plan as it was then if that plan's
-    // kernel has an item form (lcfir::fft_items_capable; unit_B = 0: no table),
-    // and the longest row (the chunk rule).
+    // kernel has an item form (lcfir::fft_items_capable, or for a partitioned
+    // plan lcfir::fft_items_parts_capable; unit_B = 0: no table), and the
+    // longest row (the chunk rule).
     lcfir::FftItemUnit *d_units = nullptr;
     int64_t n_units = 0, unit_B = 0, max_n = 0;
     std::atomic<int> fusion{LCFIR_ITEMS_FUSION_GROUPS};
@@ -1632,7 +1633,7 @@ int lcfir_items_create(lcfir_ctx *ctx, const int64_t *n, const int32_t *nch, int
         const int rc = ensure_fft(ctx);
         if (rc) return rc;
         unit = ctx->fft.B;
-        if (lcfir::fft_items_capable(ctx->fft)) unit_B = unit;
+        if (lcfir::fft_items_capable(ctx->fft) || lcfir::fft_items_parts_capable(ctx->fft)) unit_B = unit;
     }
     ItemsPlan pl;
     int rc = items_plan(unit, nfiles, n, nch, pl);
@@ -1772,23 +1773,28 @@ int lcfir_items_info(const lcfir_items *it, int32_t *groups, int32_t *launches, 
 
 int lcfir_items_set_fusion(lcfir_items *it, int mode) {
     if (!it) return fail(LCFIR_EINVAL, "items is null");
-    if (mode != LCFIR_ITEMS_FUSION_AUTO && mode != LCFIR_ITEMS_FUSION_GROUPS)
+    if (mode != LCFIR_ITEMS_FUSION_AUTO && mode != LCFIR_ITEMS_FUSION_GROUPS && mode != LCFIR_ITEMS_FUSION_PARTS)
         return fail(LCFIR_EINVAL, "unknown fusion mode %d", mode);
     it->fusion = mode;
     return LCFIR_OK;
 }
 
 // The fused path's rule (include/lcfir.h, lcfir_items_filter_dev): fusion on,
-// the ctx's current plan FFT with one partition on a kernel with an item form
-// and the table's B, every row at most one launch chunk long.  Builds the plan if the ctx has none yet.
+// the ctx's current plan FFT on a kernel with an item form and the table's B,
+// every row at most one launch chunk long (fft_chunk_span: a partitioned
+// plan's 2^26 outputs included); one partition under AUTO, any number under
+// PARTS.  Builds the plan if the ctx has none yet.
 static int items_fused(lcfir_items *it, bool &fused) {
     fused = false;
-    if (it->fusion != LCFIR_ITEMS_FUSION_AUTO || it->unit_B == 0 || it->n_units == 0) return LCFIR_OK;
+    const int mode = it->fusion;
+    if (mode == LCFIR_ITEMS_FUSION_GROUPS || it->unit_B == 0 || it->n_units == 0) return LCFIR_OK;
     if (resolve_method(it->ctx) != LCFIR_METHOD_FFT) return LCFIR_OK;
     const int rc = ensure_fft(it->ctx);
     if (rc) return rc;
     const lcfir::FftPlan &plan = it->ctx->fft;
-    fused = lcfir::fft_items_capable(plan) && plan.B == it->unit_B && it->max_n <= lcfir::fft_chunk_span(plan);
+    const bool capable = lcfir::fft_items_capable(plan) ||
+                         (mode == LCFIR_ITEMS_FUSION_PARTS && lcfir::fft_items_parts_capable(plan));
+    fused = capable && plan.B == it->unit_B && it->max_n <= lcfir::fft_chunk_span(plan);
     return LCFIR_OK;
 }
 
@@ -1801,7 +1807,9 @@ int lcfir_items_filter_launches(lcfir_items *it, int32_t *filter_launches, int64
     if (rc) return rc;
     if (fused) {
         const int64_t per = lcfir::fft_max_units(it->ctx->fft);
-        *filter_launches = (int32_t)std::min<int64_t>((it->n_units + per - 1) / per, INT32_MAX);
+        // parts launches per slice of the table (parts = 1: the slices)
+        *filter_launches =
+            (int32_t)std::min<int64_t>((it->n_units + per - 1) / per * (int64_t)it->ctx->fft.parts, INT32_MAX);
         *fused_units = it->n_units;
     } else {
         *filter_launches = (int32_t)it->launches.size();
@@ -1810,8 +1818,12 @@ int lcfir_items_filter_launches(lcfir_items *it, int32_t *filter_launches, int64
     return LCFIR_OK;
 }
 
-// One launch for all groups: the item form of the plan's kernel over the
-// per-unit table (lcfir::fft_launch_items).  Stream bookkeeping as run_filter.
+// One launch for all groups (one per partition of a partitioned plan): the item
+// form of the plan's kernel over the per-unit table (lcfir::fft_launch_items).
+// Stream bookkeeping as run_filter, and its scratch layout: the park slab
+// first, then a partitioned plan's f64 partial sums -- here one double per
+// arena float, every row's slice at the row's own offset (rows start 16-byte
+// aligned in floats, so their slices start 32-byte aligned).
 static int items_filter_fused(lcfir_items *it, hipStream_t s) {
     lcfir_ctx *ctx = it->ctx;
     note_stream(ctx, s);
@@ -1828,14 +1840,20 @@ static int items_filter_fused(lcfir_items *it, hipStream_t s) {
     p.half = ctx->half;
     p.peak_stride = 1;
     const size_t npark = lcfir::fft32_park_doubles(ctx->fft);
-    if (npark > 0) {
+    const size_t nsum = ctx->fft.parts > 1 ? (size_t)it->arena : 0;
+    const size_t need = npark + nsum;
+    if (need > 0) {
         bool capture_error = false;
-        double *base = stream_scratch(ctx, s, npark, capture_error);
+        double *base = stream_scratch(ctx, s, need, capture_error);
         if (capture_error)
             return fail(LCFIR_EINVAL, "FFT scratch of %zu doubles is not allocated on this stream: run "
-                        "an eager call of this shape on it before HIP graph capture", npark);
-        if (!base) return fail(LCFIR_ENOMEM, "FFT scratch of %zu doubles", npark);
-        p.park = reinterpret_cast<double2 *>(base);
+                        "an eager call of this shape on it before HIP graph capture", need);
+        if (!base && nsum > 0)
+            return fail(LCFIR_ENOMEM, "FFT scratch of %zu doubles (one per arena float for the fused partitioned "
+                        "launches; LCFIR_ITEMS_FUSION_GROUPS needs one group's at a time)", need);
+        if (!base) return fail(LCFIR_ENOMEM, "FFT scratch of %zu doubles", need);
+        p.park = npark ? reinterpret_cast<double2 *>(base) : nullptr;
+        p.y64 = nsum ? base + npark : nullptr;
     }
     std::string err;
     if (!lcfir::fft_launch_items(ctx->fft, p, it->d_units, it->n_units, s, err))

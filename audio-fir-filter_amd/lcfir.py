@@ -360,7 +360,8 @@ Filter.filter_window_dev = _filter_window_dev
 Filter.filter_window_norm_dev = _filter_window_norm_dev
 
 
-ITEMS_FUSION = {"auto": 0, "groups": 1}
+# (2 is kept unknown: lcfir.h, LCFIR_ITEMS_FUSION_PARTS)
+ITEMS_FUSION = {"auto": 0, "groups": 1, "parts": 3}
 # lcfir_item_unit: one (row, segment) of the fused filter launch's table
 ITEM_UNIT = np.dtype([("off", np.int64), ("seg", np.int32), ("n", np.int32)])
 
@@ -370,7 +371,8 @@ class ItemSet:
     batch scenario, main.cp:132-147) laid out as zero-padded rows of one arena
     and filtered in one launch per group of equal unit count (the default) or
     one for all groups (set_fusion("auto"): the per-unit table; single-partition
-    FFT plans on the LDS-column kernels), with ragged
+    FFT plans on the LDS-column kernels; set_fusion("parts"): partitioned plans
+    on those kernels too, one launch per partition), with ragged
     peak / normalize / codec passes of one launch each.  `nframes[f]` frames
     and `nch[f]` channels per file.  Serves one stream at a time."""
 
@@ -435,7 +437,10 @@ class ItemSet:
 
     def set_fusion(self, mode):
         """"groups" (the default): the per-group launches; "auto": one filter
-        launch for all groups where the plan allows."""
+        launch for all groups where the plan allows (single-partition plans on
+        the LDS-column kernels); "parts": as "auto", and a partitioned plan on
+        those kernels runs one launch per partition for all groups (its f64
+        partial sums take arena_floats doubles of the stream's scratch)."""
         _check(load().lcfir_items_set_fusion(self._h, ITEMS_FUSION[mode] if isinstance(mode, str) else int(mode)))
 
     def filter_launches(self):

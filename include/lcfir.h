@@ -413,10 +413,11 @@ typedef struct lcfir_items lcfir_items;
  * *outputs for the FFT method, 4 096 for the direct form), allocates an input
  * and an output arena of the planned length on the ctx's device, zeroes the
  * input arena once and uploads the tile tables the passes below walk.  If the
- * ctx's plan is then a single-partition FFT plan on an LDS-column kernel
- * (LCFIR_FFT_KERNEL_L16 or _L32_PARK), the per-unit table
+ * ctx's plan is then an FFT plan on an LDS-column kernel (LCFIR_FFT_KERNEL_L16
+ * or _L32_PARK), of one partition or of several, the per-unit table
  * (lcfir_items_unit_table at that plan's outputs per unit) is uploaded too and
- * its B recorded: what the fused filter launch below walks.  The
+ * its B recorded: what the fused filter launches below walk (16 bytes per
+ * entry; the table alone changes nothing about which path a call takes).  The
  * ctx must outlive the item set's lcfir_items_filter_dev calls.  An item set
  * serves one stream at a time: calls on one stream run in order; the caller
  * orders a change of stream itself. */
@@ -450,20 +451,46 @@ int lcfir_items_info(const lcfir_items *items, int32_t *groups, int32_t *launche
  * chunk long (the `chunk` tuning; 2^28 outputs by default); a max_units
  * tuning splits it into consecutive launches of that many entries.  Otherwise
  * (the direct method, a partitioned plan, a register-kernel plan, a seg_len
- * changed after create, a row longer than a chunk) the per-group path.  Both
- * paths give the same bytes in [0, n) of every row.  Allocates nothing
- * beyond what the filter launches do, so it captures into a HIP graph under
- * their rule (an eager call on the stream first sizes the FFT scratch). */
+ * changed after create, a row longer than a chunk) the per-group path.
+ * Fused partitioned path (LCFIR_ITEMS_FUSION_PARTS only): a plan of P > 1
+ * partitions on an LDS-column kernel runs P launches over the same table, in
+ * the order first, add ... add, last, each with the parameters the per-file
+ * call gives that partition of that unit (half - part * the partition's taps;
+ * one chunk, start = 0, x_hi = end = n), so the partial sums, their adds and
+ * the final rounding are lcfir_filter_channels_dev's and outputs [0, n) are
+ * its bytes.  The f64 partial sums live in the stream's FFT scratch, one
+ * double per arena float (each row's slice at the row's own arena offset),
+ * behind the park kernel's slab: the call grows that scratch to
+ * 8 * arena_floats bytes (+ the slab) where the per-group path needs one
+ * group's rows at a time; if that allocation fails the call returns
+ * LCFIR_ENOMEM and LCFIR_ITEMS_FUSION_GROUPS is the way out.  The first
+ * launch writes every output of every row's [0, n) before the later ones read
+ * it, so stale scratch never reaches an output.  Taken when the plan is FFT,
+ * not on the register kernel, has the table's B, and every row is at most one
+ * launch chunk long (2^26 outputs for a partitioned plan, or the `chunk`
+ * tuning if lower); with one partition PARTS is exactly AUTO's launch; a
+ * max_units tuning splits the table as above, P launches per slice.
+ * Every path gives the same bytes in [0, n) of every row.  Allocates nothing
+ * beyond the stream's FFT scratch, as the filter launches do, so it captures
+ * into a HIP graph under their rule (an eager call on the stream first sizes
+ * the FFT scratch; a capture that would have to grow it is LCFIR_EINVAL). */
 int lcfir_items_filter_dev(lcfir_items *items, float *d_peak, void *stream);
-/* How lcfir_items_filter_dev picks its path: GROUPS (the default: the fused
- * launch's step time is not measured yet) always runs the
- * per-group launches, AUTO fuses where the rule above allows. */
+/* How lcfir_items_filter_dev picks its path: GROUPS (the default, DESIGN.md
+ * s4.8) always runs the per-group launches, AUTO fuses single-partition plans
+ * where the rule above allows and leaves a partitioned plan on the per-group
+ * path, PARTS does what AUTO does and also fuses partitioned plans on the
+ * LDS-column kernels (one launch per partition).  PARTS is 3, not 2: callers
+ * and tests written against the two-mode header use 2 as "an unknown mode",
+ * and it stays LCFIR_EINVAL, like every other value. */
 #define LCFIR_ITEMS_FUSION_AUTO 0
 #define LCFIR_ITEMS_FUSION_GROUPS 1
+#define LCFIR_ITEMS_FUSION_PARTS 3
 int lcfir_items_set_fusion(lcfir_items *items, int mode);
 /* What the next lcfir_items_filter_dev would launch under the ctx's plan as it
- * is now: the fused path's launches (1 unless a max_units tuning splits the
- * table) and the table entries they run; on the per-group path
+ * is now: the fused path's launches (parts * ceil(entries / max_units): 1 for
+ * a single-partition plan unless a max_units tuning splits the table, one per
+ * partition and slice on the fused partitioned path) and the table entries
+ * they run; on the per-group path
  * lcfir_items_info's launches (the plan's group launches; each still runs one
  * kernel per chunk and partition) and 0 entries.  The peak launch is not
  * counted. */

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Rate of a batch of short files four ways, on one device in one process:
+"""Rate of a batch of short files five ways, on one device in one process:
 
   (a) eager    per-file lcfir_filter_window_dev calls on one stream
                (batch.BatchRunner, one lane: fused peak, the normalize riding
@@ -14,7 +14,12 @@
                in the output, and --family lds), one ragged peak launch, one
                ragged normalize;
   (d) items_groups  a second item set with fusion="groups": one filter launch
-               per group of equal unit count, then the same two ragged passes.
+               per group of equal unit count, then the same two ragged passes;
+  (e) items_parts   a third item set with fusion="parts": (c)'s launch for a
+               single-partition plan, and for a partitioned plan on an
+               LDS-column kernel (--fs 96000: 38 401 taps, two partitions on
+               the park kernel) one launch per partition for all groups, where
+               (c) and (d) both run groups x partitions launches.
 
 A step is filter + per-file peak + the per-file normalize decision for every
 file of the batch.  Workloads: BASELINE config 1's shape repeated (--files
@@ -24,8 +29,8 @@ the device pre-rolled, then the arrangements are timed in alternation
 (--rounds windows each, HIP events around --steps steps on the stream that
 runs them, and a host clock that stops after a device synchronise beside
 them); the rate is the batch's samples x steps / the window's event time.
-Before and after timing, (c)'s and (d)'s outputs and peaks are compared with
-(a)'s bit for bit.
+Before and after timing, (c)'s, (d)'s and (e)'s outputs and peaks are compared
+with (a)'s bit for bit.
 Prints a table and one JSON line; not part of bench.py.
 """
 import argparse
@@ -52,7 +57,9 @@ def build(torch, lcfir, batch, flt, files, dev, lanes):
     ib = batch.ItemBatch(ibe, files, fusion="auto")
     ibe_g = batch.DeviceItemBackend(flt, dev)
     ib_g = batch.ItemBatch(ibe_g, files, fusion="groups")
-    return be_a, run_a, be_b, run_b, ibe, ib, ibe_g, ib_g
+    ibe_p = batch.DeviceItemBackend(flt, dev)
+    ib_p = batch.ItemBatch(ibe_p, files, fusion="parts")
+    return be_a, run_a, be_b, run_b, ibe, ib, ibe_g, ib_g, ibe_p, ib_p
 
 
 def window(torch, stream, fn, calls):
@@ -77,13 +84,13 @@ def measure(args, torch, lcfir, batch, np, name, files, taps, dev):
     flt = lcfir.Filter(taps, device=dev.index or 0, method="auto")
     if args.family != "default":
         flt.set_fft_family(args.family)
-    be_a, run_a, be_b, run_b, ibe, ib, ibe_g, ib_g = build(torch, lcfir, batch, flt, files, dev, args.lanes)
+    be_a, run_a, be_b, run_b, ibe, ib, ibe_g, ib_g, ibe_p, ib_p = build(torch, lcfir, batch, flt, files, dev, args.lanes)
     samples = sum(f.size for f in files)
-    sets = {"items": ib, "items_groups": ib_g}
+    sets = {"items": ib, "items_groups": ib_g, "items_parts": ib_p}
     launched = {k: v.b.items.filter_launches() for k, v in sets.items()}
 
     def same_as_eager():
-        """both item sets against the per-file calls, outputs and peaks"""
+        """every item set against the per-file calls, outputs and peaks"""
         run_a.step()
         for v in sets.values():
             v.step()
@@ -113,6 +120,7 @@ def measure(args, torch, lcfir, batch, np, name, files, taps, dev):
         "graphed": (be_b.streams[0], graphed.replay, replays, replays * per_replay),
         "items": (s_a, ib.step, args.steps, args.steps),
         "items_groups": (s_a, ib_g.step, args.steps, args.steps),
+        "items_parts": (s_a, ib_p.step, args.steps, args.steps),
     }
     # pre-roll: untimed work until the clock has settled, every arrangement warm
     t0 = time.perf_counter()
@@ -136,6 +144,7 @@ def measure(args, torch, lcfir, batch, np, name, files, taps, dev):
            "launches": ib.layout["launches"], "items_equal_per_file_calls": all(same.values()),
            "equal_per_file_calls": same, "filter_launches": {k: v[0] for k, v in launched.items()},
            "fused_units": launched["items"][1], "cus": cus, "grid_rounds": -(-launched["items"][1] // cus),
+           "fused_units_parts": launched["items_parts"][1],
            "rounds": args.rounds,
            "steps_per_window": {k: v[3] for k, v in arrangements.items()}}
     for k, v in ms.items():
@@ -148,6 +157,7 @@ def measure(args, torch, lcfir, batch, np, name, files, taps, dev):
     torch.cuda.synchronize()
     ibe.close()
     ibe_g.close()
+    ibe_p.close()
     flt.close()
     return out
 
@@ -190,9 +200,10 @@ def main():
         results.append(r)
         print(f"{name}: {r['files']} files, {r['samples_per_step']} samples/step, {r['ntaps']} taps, "
               f"unit {r['unit']} ({r['kernel']}), {r['groups']} groups, filter launches {r['filter_launches']}, "
-              f"{r['fused_units']} fused units = {r['grid_rounds']} rounds of {r['cus']} CUs, "
+              f"{r['fused_units']} fused units = {r['grid_rounds']} rounds of {r['cus']} CUs "
+              f"({r['fused_units_parts']} under parts), "
               f"same bytes: {r['equal_per_file_calls']}")
-        for k in ("eager", "graphed", "items", "items_groups"):
+        for k in ("eager", "graphed", "items", "items_groups", "items_parts"):
             v = r[k]
             print(f"  {k:12s} {v['step_ms_median']:9.4f} ms/step (min {v['step_ms_min']:.4f}, max "
                   f"{v['step_ms_max']:.4f}; host clock {v['host_step_ms_median']:.4f})  "
