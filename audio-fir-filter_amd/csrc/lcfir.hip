@@ -1581,6 +1581,33 @@ static void items_unit_fill(int64_t B, const int64_t *n, const int32_t *nch, con
         }
 }
 
+// lcfir_items_unit_files: the file of every entry items_unit_fill writes, in its order
+static void items_unit_files_fill(int64_t B, const int64_t *n, const int32_t *nch, const ItemsPlan &pl,
+                                  int32_t *out) {
+    for (const int32_t f : pl.order) {
+        const int64_t u = (n[f] + B - 1) / B * (int64_t)nch[f];
+        std::fill(out, out + u, f);
+        out += u;
+    }
+}
+
+int lcfir_items_unit_files(int64_t B, int32_t nfiles, const int64_t *n, const int32_t *nch, int64_t *nunits,
+                           int32_t *file, int64_t cap) {
+    if (!nunits) return fail(LCFIR_EINVAL, "nunits is null");
+    *nunits = 0;
+    ItemsPlan pl;
+    int rc = items_plan(B, nfiles, n, nch, pl);
+    if (rc) return rc;
+    int64_t total = 0;
+    rc = items_unit_count(B, n, nch, pl, total);
+    if (rc) return rc;
+    *nunits = total;
+    if (cap < total) return fail(LCFIR_EINVAL, "%lld entries do not fit cap = %lld", (long long)total, (long long)cap);
+    if (total > 0 && !file) return fail(LCFIR_EINVAL, "file is null");
+    items_unit_files_fill(B, n, nch, pl, file);
+    return LCFIR_OK;
+}
+
 int lcfir_items_unit_table(int64_t B, int32_t nfiles, const int64_t *n, const int32_t *nch, int64_t *nunits,
                            lcfir_item_unit *entries, int64_t cap) {
     if (!nunits) return fail(LCFIR_EINVAL, "nunits is null");

@@ -116,6 +116,7 @@ _SIGNATURES = {
                           ctypes.POINTER(_c_i64)], _c_int),
     "lcfir_items_filter_dev": ([_vp, _vp, _vp], _c_int),
     "lcfir_items_unit_table": ([_c_i64, _c_i32, _vp, _vp, ctypes.POINTER(_c_i64), _vp, _c_i64], _c_int),
+    "lcfir_items_unit_files": ([_c_i64, _c_i32, _vp, _vp, ctypes.POINTER(_c_i64), _vp, _c_i64], _c_int),
     "lcfir_items_set_fusion": ([_vp, _c_int], _c_int),
     "lcfir_items_filter_launches": ([_vp, ctypes.POINTER(_c_i32), ctypes.POINTER(_c_i64)], _c_int),
     "lcfir_items_normalize_dev": ([_vp, _vp, _c_int, _vp], _c_int),
@@ -432,6 +433,27 @@ class ItemSet:
             cap = total.value
         out = np.zeros(int(cap), ITEM_UNIT)
         _check(lib.lcfir_items_unit_table(int(B), int(n.size), n.ctypes.data, c.ctypes.data, ctypes.byref(total),
+                                          out.ctypes.data, int(cap)))
+        return out[:total.value]
+
+    @staticmethod
+    def unit_files(B: int, nframes, nch, cap=None) -> np.ndarray:
+        """lcfir_items_unit_files, a pure function (no device): the file of
+        every unit_table entry, in its order, as int32.  cap as unit_table's."""
+        n = np.ascontiguousarray(np.asarray(nframes, dtype=np.int64).reshape(-1))
+        c = np.ascontiguousarray(np.asarray(nch, dtype=np.int32).reshape(-1))
+        if n.size != c.size:
+            raise ValueError("nframes and nch differ in length")
+        lib, total = load(), ctypes.c_int64()
+        if cap is None:
+            rc = lib.lcfir_items_unit_files(int(B), int(n.size), n.ctypes.data, c.ctypes.data, ctypes.byref(total),
+                                            None, 0)
+            if total.value > 0:
+                rc = 0  # the total only: cap = 0 is too small by design
+            _check(rc)
+            cap = total.value
+        out = np.full(int(cap), -1, np.int32)
+        _check(lib.lcfir_items_unit_files(int(B), int(n.size), n.ctypes.data, c.ctypes.data, ctypes.byref(total),
                                           out.ctypes.data, int(cap)))
         return out[:total.value]
 

@@ -406,6 +406,16 @@ typedef struct lcfir_item_unit {
 } lcfir_item_unit;
 int lcfir_items_unit_table(int64_t B, int32_t nfiles, const int64_t *n, const int32_t *nch, int64_t *nunits,
                            lcfir_item_unit *entries, int64_t cap);
+/* The file of every entry of lcfir_items_unit_table, in its order: file[u] is
+ * the index (into n / nch) of the file whose row entry u belongs to.  A pure
+ * function (no device) with the unit table's count, order and cap rules:
+ * *nunits always receives the total, file (nullable when cap = 0) is written
+ * only if cap >= the total, else nothing is written and the call returns
+ * LCFIR_EINVAL; files with n = 0 or nch = 0 have no entry.  No launch reads it
+ * yet: it is the slot table a per-file peak fused into the item kernels needs
+ * (scripts/variants/items_peak/). */
+int lcfir_items_unit_files(int64_t B, int32_t nfiles, const int64_t *n, const int32_t *nch, int64_t *nunits,
+                           int32_t *file, int64_t cap);
 
 typedef struct lcfir_items lcfir_items;
 /* Plans nfiles files (n[f] frames, nch[f] channels) with unit = the outputs
