@@ -562,6 +562,16 @@ class ItemBackend:
         """[nch][n] view of a file's block of the output arena"""
         raise NotImplementedError
 
+    def gather(self, ptrs, strides):
+        """TensorBatch: file f's rows at device address ptrs[f] (strides[f]
+        floats between channels) into the input arena, one launch"""
+        raise NotImplementedError
+
+    def scatter(self, peaks, force: bool, ptrs, strides):
+        """TensorBatch: every file's output rows to ptrs[f], rescaled on the
+        way by normalize()'s rule; the arena stays unscaled"""
+        raise NotImplementedError
+
 
 class ItemBatch:
     """A batch of files of different lengths and channel counts through one
@@ -676,8 +686,93 @@ class DeviceItemBackend(ItemBackend):
     def rows(self, offset, nch, stride, n):
         return self.y[offset:offset + nch * stride].view(nch, stride)[:, :n]
 
+    def gather(self, ptrs, strides):
+        self.items.gather_dev(ptrs, strides, self._sp())
+
+    def scatter(self, peaks, force, ptrs, strides):
+        self.items.scatter_scaled_dev(peaks, force, ptrs, strides, self._sp())
+
     def close(self):
         self.x = self.y = None
         if self.items is not None:
             self.items.close()
             self.items = None
+
+
+class TensorBatch:
+    """A ragged list of float32 CUDA tensors through one item set, end to end
+    on the device: per step one gather launch (the tensors' rows into the
+    input arena), the filter launches of `fusion` (ItemBatch's meaning), one
+    ragged peak launch and one scatter launch that rescales on the way out
+    (file f by 1 / peak[f] iff peak[f] > 1 or `normalize`: ItemBatch's
+    results, bit for bit), whatever the number of tensors.  Runs on the
+    current torch stream; the only host wait is for a table slot of the step
+    before last.
+
+    tensors: each [nch_i, n_i] or [n_i], float32, on flt's device, last
+    dimension contiguous and channels at least n_i apart; zero-length ones are
+    allowed.  `outputs` holds one tensor of each input's shape, allocated
+    once and rewritten by every step; `peaks[f]` is file f's max|y|.  The
+    inputs are read again by every step, so a caller may refill them between
+    steps."""
+
+    def __init__(self, flt, tensors, normalize: bool = False, fusion: str = "groups", backend: ItemBackend = None):
+        import torch
+        if fusion not in ("auto", "groups", "parts"):
+            raise ValueError(f"fusion must be 'auto', 'groups' or 'parts', got {fusion!r}")
+        dev = torch.device("cuda", int(flt.device))
+        self.inputs = list(tensors)
+        for i, t in enumerate(self.inputs):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+                raise ValueError(f"tensor {i}: need a float32 torch tensor, got "
+                                 f"{t.dtype if isinstance(t, torch.Tensor) else type(t)}")
+            if t.dim() not in (1, 2):
+                raise ValueError(f"tensor {i}: need [nch, n] or [n], got shape {tuple(t.shape)}")
+            n = int(t.shape[-1])
+            if n > 1 and t.stride(-1) != 1:
+                raise ValueError(f"tensor {i}: the last dimension must have stride 1, got {t.stride(-1)}")
+            if t.dim() == 2 and t.shape[0] > 1 and n > 0 and t.stride(0) < n:
+                raise ValueError(f"tensor {i}: channel stride {t.stride(0)} is below its {n} frames")
+            if t.device != dev:
+                raise ValueError(f"tensor {i}: is on {t.device}, the filter is on {dev}")
+        self.b = backend if backend is not None else DeviceItemBackend(flt, dev)
+        self.normalize = normalize
+        self.fusion = fusion
+        self.nframes = [int(t.shape[-1]) for t in self.inputs]
+        self.nch = [int(t.shape[0]) if t.dim() == 2 else 1 for t in self.inputs]
+        self.layout = self.b.create(self.nframes, self.nch)
+        self.b.set_fusion(fusion)
+        self.outputs = [torch.empty(tuple(t.shape), dtype=torch.float32, device=t.device) for t in self.inputs]
+        self._src, self._src_stride = self._spans(self.inputs)
+        self._dst, self._dst_stride = self._spans(self.outputs)
+        self.peaks = self.b.new_peaks(len(self.inputs))
+        self.steps = 0
+
+    def _spans(self, tensors):
+        """(address of channel 0, floats between channels) per tensor; 0, 0 for one without samples"""
+        live = [t.numel() > 0 for t in tensors]
+        return ([t.data_ptr() if ok else 0 for t, ok in zip(tensors, live)],
+                [int(t.stride(0)) if ok and t.dim() == 2 else int(t.shape[-1]) if ok else 0
+                 for t, ok in zip(tensors, live)])
+
+    def step(self):
+        self.b.gather(self._src, self._src_stride)
+        self.b.zero_peaks(self.peaks)
+        self.b.filter(self.peaks)
+        self.b.scatter(self.peaks, self.normalize, self._dst, self._dst_stride)
+        self.steps += 1
+
+    def close(self):
+        if hasattr(self.b, "close"):
+            self.b.close()
+
+
+def filter_tensors(flt, tensors, normalize: bool = False, fusion: str = "groups"):
+    """One TensorBatch step: the filtered (and per-file rescaled) tensors, one
+    per input.  The item set is released once the step has finished."""
+    tb = TensorBatch(flt, tensors, normalize=normalize, fusion=fusion)
+    try:
+        tb.step()
+        return tb.outputs
+    finally:
+        tb.close()  # lcfir_items_destroy waits for the stream the step ran on

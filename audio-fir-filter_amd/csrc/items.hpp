@@ -6,10 +6,12 @@
 // shorter row's outputs [n_f, N_g) hold the filter's ringing tail.  The fused
 // peak would take them in; the per-file post-passes (ProcessFile.cp:91-101)
 // and the codec either side (ProcessFile.cp:40-41, :115-117) therefore get
-// forms that stop at each file's own n_f.  All four walk a flat tile table
+// forms that stop at each file's own n_f, and so do the two passes that move
+// rows between the arenas and tensors of the caller's.  All walk a flat tile table
 // built on the host when the item set is created:
 //
-//   row passes   (peak, normalize): tile -> (arena offset, floats, file),
+//   row passes   (peak, normalize, gather, scatter):
+//                                   tile -> (arena offset, floats, file),
 //                                   kItemRowTile floats of one row;
 //   codec passes (decode, encode):  tile -> (first interleaved sample, samples,
 //                                   file), kItemPcmTile samples of one file.
@@ -123,6 +125,134 @@ __global__ __launch_bounds__(kItemThreads) void items_normalize_kernel(float *__
         }
         const int r = n4 * 4 + (int)threadIdx.x;
         if (r < tl.count) p[r] = scale_one(p[r], gain);
+    }
+}
+
+// Per call of the tensor passes: where file f's rows sit in the caller's own
+// memory (channel c at ptr + c * stride; only 4-byte alignment is asked of it).
+struct ItemSpan {
+    float *ptr;
+    int64_t stride;
+};
+
+constexpr int kItemDwordLoads = 16; // dword loads in flight per thread where the caller's side is unaligned
+
+// A row tile's place in the caller's memory: the tile's channel and position
+// in its row follow from the two tables (rows of a file are `stride` apart in
+// the arena, so the quotient is the channel), wave-uniform per tile.
+__device__ __forceinline__ float *item_span_ptr(const ItemTile &tl, const ItemFile &fl, const ItemSpan &sp) {
+    const int64_t rel = tl.first - fl.off;
+    const int64_t c = rel / fl.stride;
+    const int64_t t0 = rel - c * fl.stride;
+    return sp.ptr + c * sp.stride + t0;
+}
+
+// The way in for rows that already sit in device memory of the caller's:
+// floats [t0, t0 + count) of row c of span[f] go to the tile's place in the
+// input arena.  Values are only moved (as 32-bit words, so every bit pattern
+// survives), and only [0, n_f) of a row is written: the padding stays zero.
+// The arena side is 16-byte aligned; where the source is too the tile moves
+// float4s like the other row passes, else dwords, sixteen in flight.
+__global__ __launch_bounds__(kItemThreads, 8) void items_gather_kernel(float *__restrict__ x,
+                                                                    const ItemTile *__restrict__ tiles,
+                                                                    int64_t ntiles,
+                                                                    const ItemFile *__restrict__ files,
+                                                                    const ItemSpan *__restrict__ span) {
+    for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        const ItemTile tl = tiles[t];
+        const uint32_t *__restrict__ src =
+            reinterpret_cast<const uint32_t *>(item_span_ptr(tl, files[tl.file], span[tl.file]));
+        uint32_t *__restrict__ dst = reinterpret_cast<uint32_t *>(x + tl.first);
+        if ((reinterpret_cast<uintptr_t>(src) & 15) == 0) {
+            const uint4 *__restrict__ s4 = reinterpret_cast<const uint4 *>(src);
+            uint4 *__restrict__ d4 = reinterpret_cast<uint4 *>(dst);
+            const int n4 = tl.count >> 2;
+            uint4 v[kItemLoads];
+#pragma unroll
+            for (int u = 0; u < kItemLoads; ++u) {
+                const int i = (int)threadIdx.x + u * kItemThreads;
+                v[u] = i < n4 ? s4[i] : make_uint4(0u, 0u, 0u, 0u);
+            }
+#pragma unroll
+            for (int u = 0; u < kItemLoads; ++u) {
+                const int i = (int)threadIdx.x + u * kItemThreads;
+                if (i < n4) d4[i] = v[u];
+            }
+            const int r = n4 * 4 + (int)threadIdx.x; // the row's last 1-3 floats
+            if (r < tl.count) dst[r] = src[r];
+        } else {
+            uint32_t v[kItemDwordLoads];
+#pragma unroll
+            for (int u = 0; u < kItemDwordLoads; ++u) {
+                const int i = (int)threadIdx.x + u * kItemThreads;
+                v[u] = i < tl.count ? src[i] : 0u;
+            }
+#pragma unroll
+            for (int u = 0; u < kItemDwordLoads; ++u) {
+                const int i = (int)threadIdx.x + u * kItemThreads;
+                if (i < tl.count) dst[i] = v[u];
+            }
+        }
+    }
+}
+
+// The way out, with items_normalize_kernel's rescale on the way: file f's rows
+// [0, n_f) of the output arena go to span[f] as scale_one(y, 1 / peak[f]) iff
+// (peak[f] > 1 or force) and peak[f] > 0, else as they are (peak == nullptr: a
+// plain copy out).  The arena is left unscaled; the peak is read once per tile.
+// The aligned / dword split is taken on the destination here.
+__global__ __launch_bounds__(kItemThreads, 8) void items_scatter_scaled_kernel(const float *__restrict__ y,
+                                                                            const ItemTile *__restrict__ tiles,
+                                                                            int64_t ntiles,
+                                                                            const ItemFile *__restrict__ files,
+                                                                            const ItemSpan *__restrict__ span,
+                                                                            const unsigned *__restrict__ peak,
+                                                                            int force) {
+    for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        const ItemTile tl = tiles[t];
+        const float pk = peak ? __uint_as_float(peak[tl.file]) : 0.0f;
+        const bool scale = (pk > 1.0f || force) && pk > 0.0f;
+        const double gain = scale ? 1.0 / (double)pk : 1.0;
+        const float *__restrict__ src = y + tl.first;
+        float *__restrict__ dst = item_span_ptr(tl, files[tl.file], span[tl.file]);
+        if ((reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
+            const float4 *__restrict__ s4 = reinterpret_cast<const float4 *>(src);
+            float4 *__restrict__ d4 = reinterpret_cast<float4 *>(dst);
+            const int n4 = tl.count >> 2;
+            float4 v[kItemLoads];
+#pragma unroll
+            for (int u = 0; u < kItemLoads; ++u) {
+                const int i = (int)threadIdx.x + u * kItemThreads;
+                v[u] = i < n4 ? s4[i] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            }
+#pragma unroll
+            for (int u = 0; u < kItemLoads; ++u) {
+                const int i = (int)threadIdx.x + u * kItemThreads;
+                if (i < n4) {
+                    if (scale) {
+                        v[u].x = scale_one(v[u].x, gain);
+                        v[u].y = scale_one(v[u].y, gain);
+                        v[u].z = scale_one(v[u].z, gain);
+                        v[u].w = scale_one(v[u].w, gain);
+                    }
+                    d4[i] = v[u];
+                }
+            }
+            const int r = n4 * 4 + (int)threadIdx.x;
+            if (r < tl.count) dst[r] = scale ? scale_one(src[r], gain) : src[r];
+        } else {
+            float v[kItemDwordLoads];
+#pragma unroll
+            for (int u = 0; u < kItemDwordLoads; ++u) {
+                const int i = (int)threadIdx.x + u * kItemThreads;
+                v[u] = i < tl.count ? src[i] : 0.0f;
+            }
+#pragma unroll
+            for (int u = 0; u < kItemDwordLoads; ++u) {
+                const int i = (int)threadIdx.x + u * kItemThreads;
+                if (i < tl.count) dst[i] = scale ? scale_one(v[u], gain) : v[u];
+            }
+        }
     }
 }
 

@@ -115,6 +115,15 @@ struct lcfir_items {
     hipEvent_t pcm_done[kPcmSlots] = {};
     bool pcm_pending[kPcmSlots] = {};
     int pcm_next = 0;
+    // The tensor calls' per-call table (lcfir_items_gather_dev,
+    // _scatter_scaled_dev: pointer and stride per file), by the same route.
+    // Device table, slots and events are allocated at the first such call.
+    static constexpr int kSpanSlots = 2;
+    lcfir::ItemSpan *d_span = nullptr;
+    lcfir::ItemSpan *h_span[kSpanSlots] = {};
+    hipEvent_t span_done[kSpanSlots] = {};
+    bool span_pending[kSpanSlots] = {};
+    int span_next = 0;
     std::mutex mu;
     std::vector<hipStream_t> used; // every stream a call on this item set went to
 };
@@ -1774,6 +1783,11 @@ int lcfir_items_destroy(lcfir_items *it) {
         if (it->h_pcm[k]) (void)hipHostFree(it->h_pcm[k]);
         if (it->pcm_done[k]) (void)hipEventDestroy(it->pcm_done[k]);
     }
+    if (it->d_span) (void)hipFree(it->d_span);
+    for (int k = 0; k < lcfir_items::kSpanSlots; ++k) {
+        if (it->h_span[k]) (void)hipHostFree(it->h_span[k]);
+        if (it->span_done[k]) (void)hipEventDestroy(it->span_done[k]);
+    }
     delete it;
     return LCFIR_OK;
 }
@@ -1999,6 +2013,92 @@ int lcfir_items_encode_pcm_scaled_dev(lcfir_items *it, const float *d_peak, int 
                        dim3(lcfir::kItemThreads), 0, s, it->d_out, it->d_pcm_tiles, it->n_pcm_tiles, it->d_files,
                        it->d_pcm, reinterpret_cast<const unsigned *>(d_peak), force ? 1 : 0,
                        reinterpret_cast<uint8_t *>(d_bytes));
+    LCFIR_HIP(hipGetLastError());
+    return LCFIR_OK;
+}
+
+// The tensor calls' per-call table: check every live file's pointer and
+// stride, fill the next page-locked slot and queue its copy to d_span on s.
+// The device table, the slots and their events are allocated here at the
+// first call, not in lcfir_items_create.
+static int items_span_table(lcfir_items *it, const float *const *ptr, const int64_t *stride, hipStream_t s) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs == hipStreamCaptureStatusActive)
+        return fail(LCFIR_EINVAL, "the item set's gather and scatter calls cannot be captured into a HIP graph");
+    const size_t arena_bytes = sizeof(float) * (size_t)it->arena;
+    for (int32_t f = 0; f < it->nfiles; ++f) {
+        if (it->group[(size_t)f] < 0) continue;
+        const int64_t n = it->n[(size_t)f];
+        const int32_t nch = it->nch[(size_t)f];
+        if (!ptr[f]) return fail(LCFIR_EINVAL, "file %d: null pointer", f);
+        if (reinterpret_cast<uintptr_t>(ptr[f]) & 3) return fail(LCFIR_EINVAL, "file %d: pointer not 4-byte aligned", f);
+        if (nch > 1 && stride[f] < n)
+            return fail(LCFIR_EINVAL, "file %d: channel stride %lld below its %lld frames", f, (long long)stride[f],
+                        (long long)n);
+        if (nch > 1 && stride[f] > (INT64_MAX / 8) / nch)
+            return fail(LCFIR_EINVAL, "file %d: channel stride %lld too large", f, (long long)stride[f]);
+        const size_t span = sizeof(float) * (size_t)((nch > 1 ? (int64_t)(nch - 1) * stride[f] : 0) + n);
+        if (ranges_overlap(ptr[f], span, it->d_in, arena_bytes) || ranges_overlap(ptr[f], span, it->d_out, arena_bytes))
+            return fail(LCFIR_EINVAL, "file %d: its memory overlaps the item set's arenas", f);
+    }
+    std::lock_guard<std::mutex> lk(it->mu);
+    const size_t tb = sizeof(lcfir::ItemSpan) * (size_t)it->nfiles;
+    if (!it->d_span && hipMalloc(reinterpret_cast<void **>(&it->d_span), tb) != hipSuccess) {
+        it->d_span = nullptr;
+        return fail(LCFIR_ENOMEM, "hipMalloc for the span table failed");
+    }
+    for (int k = 0; k < lcfir_items::kSpanSlots; ++k) {
+        if (!it->h_span[k] &&
+            hipHostMalloc(reinterpret_cast<void **>(&it->h_span[k]), tb, hipHostMallocDefault) != hipSuccess) {
+            it->h_span[k] = nullptr;
+            return fail(LCFIR_ENOMEM, "hipHostMalloc for the span table failed");
+        }
+        if (!it->span_done[k]) LCFIR_HIP(hipEventCreateWithFlags(&it->span_done[k], hipEventDisableTiming));
+    }
+    const int k = it->span_next;
+    if (it->span_pending[k]) LCFIR_HIP(hipEventSynchronize(it->span_done[k]));
+    it->span_pending[k] = false;
+    for (int32_t f = 0; f < it->nfiles; ++f) {
+        const bool live = it->group[(size_t)f] >= 0;
+        it->h_span[k][f] = lcfir::ItemSpan{live ? const_cast<float *>(ptr[f]) : nullptr, live ? stride[f] : 0};
+    }
+    LCFIR_HIP(hipMemcpyAsync(it->d_span, it->h_span[k], tb, hipMemcpyHostToDevice, s));
+    LCFIR_HIP(hipEventRecord(it->span_done[k], s));
+    it->span_pending[k] = true;
+    it->span_next = (k + 1) % lcfir_items::kSpanSlots;
+    return LCFIR_OK;
+}
+
+int lcfir_items_gather_dev(lcfir_items *it, const float *const *d_src, const int64_t *src_stride, void *stream) {
+    if (!it) return fail(LCFIR_EINVAL, "items is null");
+    if (it->n_row_tiles == 0) return LCFIR_OK;
+    if (!d_src || !src_stride) return fail(LCFIR_EINVAL, "null argument");
+    DeviceGuard g(it->device);
+    if (!g.ok) return fail(LCFIR_EDEVICE, "hipSetDevice(%d) failed", it->device);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int rc = items_span_table(it, d_src, src_stride, s);
+    if (rc) return rc;
+    items_note_stream(it, s);
+    hipLaunchKernelGGL(lcfir::items_gather_kernel, dim3(items_blocks(it->n_row_tiles)), dim3(lcfir::kItemThreads),
+                       0, s, it->d_in, it->d_row_tiles, it->n_row_tiles, it->d_files, it->d_span);
+    LCFIR_HIP(hipGetLastError());
+    return LCFIR_OK;
+}
+
+int lcfir_items_scatter_scaled_dev(lcfir_items *it, const float *d_peak, int force, float *const *d_dst,
+                                   const int64_t *dst_stride, void *stream) {
+    if (!it) return fail(LCFIR_EINVAL, "items is null");
+    if (it->n_row_tiles == 0) return LCFIR_OK;
+    if (!d_dst || !dst_stride) return fail(LCFIR_EINVAL, "null argument");
+    DeviceGuard g(it->device);
+    if (!g.ok) return fail(LCFIR_EDEVICE, "hipSetDevice(%d) failed", it->device);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int rc = items_span_table(it, d_dst, dst_stride, s);
+    if (rc) return rc;
+    items_note_stream(it, s);
+    hipLaunchKernelGGL(lcfir::items_scatter_scaled_kernel, dim3(items_blocks(it->n_row_tiles)),
+                       dim3(lcfir::kItemThreads), 0, s, it->d_out, it->d_row_tiles, it->n_row_tiles, it->d_files,
+                       it->d_span, reinterpret_cast<const unsigned *>(d_peak), force ? 1 : 0);
     LCFIR_HIP(hipGetLastError());
     return LCFIR_OK;
 }

@@ -122,6 +122,8 @@ _SIGNATURES = {
     "lcfir_items_normalize_dev": ([_vp, _vp, _c_int, _vp], _c_int),
     "lcfir_items_decode_pcm_dev": ([_vp, _vp, _vp, _vp, _vp], _c_int),
     "lcfir_items_encode_pcm_scaled_dev": ([_vp, _vp, _c_int, _vp, _vp, _vp, _vp], _c_int),
+    "lcfir_items_gather_dev": ([_vp, _vp, _vp, _vp], _c_int),
+    "lcfir_items_scatter_scaled_dev": ([_vp, _vp, _c_int, _vp, _vp, _vp], _c_int),
     "lcfir_dev_malloc": ([_c_int, ctypes.c_size_t, ctypes.POINTER(_vp)], _c_int),
     "lcfir_dev_free": ([_vp], _c_int),
     "lcfir_memcpy_h2d": ([_vp, _vp, ctypes.c_size_t, _vp], _c_int),
@@ -516,6 +518,29 @@ class ItemSet:
         off, fmt = self._pcm_args(byte_offset, formats)
         _check(load().lcfir_items_encode_pcm_scaled_dev(self._h, _ptr(d_peak), 1 if force else 0, _ptr(d_bytes),
                                                         off.ctypes.data, fmt.ctypes.data, stream or None))
+
+    def _span_args(self, ptrs, strides):
+        p = np.ascontiguousarray(np.asarray([int(x or 0) for x in ptrs], dtype=np.uint64))
+        st = np.ascontiguousarray(np.asarray(strides, dtype=np.int64).reshape(-1))
+        if p.size != self.nfiles or st.size != self.nfiles:
+            raise ValueError("ptrs and strides need one entry per file")
+        return p, st
+
+    def gather_dev(self, ptrs, strides, stream=0):
+        """Device rows of the caller's (file f's channel 0 at address ptrs[f],
+        strides[f] floats between its channels) -> every file's input rows,
+        one launch; bit patterns are kept, the rows' padding stays zero."""
+        p, st = self._span_args(ptrs, strides)
+        _check(load().lcfir_items_gather_dev(self._h, p.ctypes.data, st.ctypes.data, stream or None))
+
+    def scatter_scaled_dev(self, d_peak, force: bool, ptrs, strides, stream=0):
+        """Every file's output rows -> device rows of the caller's, each file
+        scaled by its own peak slot as normalize_dev would scale it (d_peak
+        None: a plain copy); the output rows stay unscaled; one launch."""
+        p, st = self._span_args(ptrs, strides)
+        _check(load().lcfir_items_scatter_scaled_dev(self._h, _ptr(d_peak) if d_peak is not None else None,
+                                                     1 if force else 0, p.ctypes.data, st.ctypes.data,
+                                                     stream or None))
 
     def close(self):
         if getattr(self, "_h", None):

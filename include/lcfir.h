@@ -522,6 +522,31 @@ int lcfir_items_decode_pcm_dev(lcfir_items *items, const void *d_bytes, const in
                                const int32_t *format, void *stream);
 int lcfir_items_encode_pcm_scaled_dev(lcfir_items *items, const float *d_peak, int force, void *d_bytes,
                                       const int64_t *byte_offset, const int32_t *format, void *stream);
+/* The way in and out for files that already sit in device memory of the
+ * caller's (torch tensors, say), one launch each whatever the file count.
+ * d_src / d_dst and the strides are host arrays of nfiles entries, copied
+ * before the call returns: entry f is the device pointer to channel 0 of file
+ * f and the floats between its channels (>= n_f when nch_f > 1, ignored for
+ * one channel); pointers need 4-byte alignment only (a 16-byte aligned row
+ * moves in 16-byte pieces, any other in 4-byte ones).  Entries of files
+ * without rows are ignored.
+ * lcfir_items_gather_dev copies [0, n_f) of every channel into the file's
+ * input rows; values are moved, not computed on, so every bit pattern arrives
+ * (NaN payloads, -0.0, subnormals), and the rows' zero padding is not touched.
+ * lcfir_items_scatter_scaled_dev copies [0, n_f) of every output row to d_dst,
+ * scaled on the way as lcfir_items_normalize_dev would scale it -- by
+ * 1 / d_peak[f] iff (d_peak[f] > 1 or force) and d_peak[f] > 0, bit for bit
+ * -- while the output rows stay unscaled; with d_peak NULL it is a plain copy
+ * (force is ignored).  Nothing outside [0, n_f) of a destination row is
+ * written.
+ * LCFIR_EINVAL: a file with rows whose pointer is NULL or not 4-byte aligned,
+ * whose stride is below n_f with nch_f > 1, or whose memory overlaps one of
+ * the item set's arenas; a call on a capturing stream (the per-call table is
+ * uploaded from the host, through page-locked slots allocated at the first of
+ * these calls, as for the codec calls). */
+int lcfir_items_gather_dev(lcfir_items *items, const float *const *d_src, const int64_t *src_stride, void *stream);
+int lcfir_items_scatter_scaled_dev(lcfir_items *items, const float *d_peak, int force,
+                                   float *const *d_dst, const int64_t *dst_stride, void *stream);
 
 /* ---- device memory / stream helpers for hosts without a GPU runtime ----- */
 int lcfir_dev_malloc(int device, size_t bytes, void **out);

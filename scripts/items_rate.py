@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Rate of a batch of short files five ways, on one device in one process:
+"""Rate of a batch of short files eight ways, on one device in one process:
 
   (a) eager    per-file lcfir_filter_window_dev calls on one stream
                (batch.BatchRunner, one lane: fused peak, the normalize riding
@@ -19,7 +19,19 @@
                single-partition plan, and for a partitioned plan on an
                LDS-column kernel (--fs 96000: 38 401 taps, two partitions on
                the park kernel) one launch per partition for all groups, where
-               (c) and (d) both run groups x partitions launches.
+               (c) and (d) both run groups x partitions launches;
+  (f) tensors       the files as float32 tensors in device memory through
+               batch.TensorBatch: one gather launch, (d)'s filter step, one
+               scatter launch that rescales on the way out into the caller's
+               output tensors;
+  (g) tensors_copies  the same tensors in, the same output tensors filled, by
+               what the library offered before (f): one copy_ per row into the
+               arena, (d)'s step with its in-place normalize, one copy_ per row
+               out;
+  (h) groups_again  (d) once more, on an item set of its own, placed last in
+               the alternation: the spread between (d) and (h) is the floor of
+               every comparison of this run and is printed with them.  (f) is
+               compared with (g).
 
 A step is filter + per-file peak + the per-file normalize decision for every
 file of the batch.  Workloads: BASELINE config 1's shape repeated (--files
@@ -29,7 +41,7 @@ the device pre-rolled, then the arrangements are timed in alternation
 (--rounds windows each, HIP events around --steps steps on the stream that
 runs them, and a host clock that stops after a device synchronise beside
 them); the rate is the batch's samples x steps / the window's event time.
-Before and after timing, (c)'s, (d)'s and (e)'s outputs and peaks are compared
+Before and after timing, the outputs and peaks of (c) to (h) are compared
 with (a)'s bit for bit.
 Prints a table and one JSON line; not part of bench.py.
 """
@@ -86,14 +98,38 @@ def measure(args, torch, lcfir, batch, np, name, files, taps, dev):
         flt.set_fft_family(args.family)
     be_a, run_a, be_b, run_b, ibe, ib, ibe_g, ib_g, ibe_p, ib_p = build(torch, lcfir, batch, flt, files, dev, args.lanes)
     samples = sum(f.size for f in files)
-    sets = {"items": ib, "items_groups": ib_g, "items_parts": ib_p}
+    ibe_2 = batch.DeviceItemBackend(flt, dev)
+    ib_2 = batch.ItemBatch(ibe_2, files, fusion="groups")
+    sets = {"items": ib, "items_groups": ib_g, "items_parts": ib_p, "groups_again": ib_2}
     launched = {k: v.b.items.filter_launches() for k, v in sets.items()}
+    # the files as tensors in device memory, and the two ways to filter them
+    d_files = [torch.from_numpy(f).to(dev) for f in files]
+    tb = batch.TensorBatch(flt, d_files, normalize=False, fusion="groups")
+    ibe_c = batch.DeviceItemBackend(flt, dev)
+    ib_c = batch.ItemBatch(ibe_c, [np.zeros_like(f) for f in files], fusion="groups")
+    rows_in = [ibe_c.x[o:o + c * st].view(c, st)[:, :n] if st else None
+               for o, c, st, n in zip(ib_c.offset, ib_c.nch, ib_c.stride, ib_c.nframes)]
+    rows_out = ib_c.results()
+    outs_c = [torch.empty_like(t) for t in d_files]
+
+    def copies_step():
+        for t, v in zip(d_files, rows_in):
+            if v is not None:
+                for c in range(t.shape[0]):
+                    v[c].copy_(t[c])
+        ib_c.step()
+        for o, v in zip(outs_c, rows_out):
+            if v is not None:
+                for c in range(o.shape[0]):
+                    o[c].copy_(v[c])
 
     def same_as_eager():
         """every item set against the per-file calls, outputs and peaks"""
         run_a.step()
         for v in sets.values():
             v.step()
+        tb.step()
+        copies_step()
         torch.cuda.synchronize()
         want = {sh.file: y.cpu().numpy() for sh, y in run_a.results()}
         pk_a = run_a.peaks.cpu().numpy()[:len(files)]
@@ -102,6 +138,10 @@ def measure(args, torch, lcfir, batch, np, name, files, taps, dev):
             pk_c = v.peaks.cpu().numpy()[:len(files)]
             ok[k] = bool(np.array_equal(pk_a.view(np.uint32), pk_c.view(np.uint32)))
             for f, y in enumerate(v.results()):
+                ok[k] = ok[k] and bool(np.array_equal(y.cpu().numpy().view(np.uint32), want[f].view(np.uint32)))
+        for k, outs, pk in (("tensors", tb.outputs, tb.peaks), ("tensors_copies", outs_c, ib_c.peaks)):
+            ok[k] = bool(np.array_equal(pk_a.view(np.uint32), pk.cpu().numpy()[:len(files)].view(np.uint32)))
+            for f, y in enumerate(outs):
                 ok[k] = ok[k] and bool(np.array_equal(y.cpu().numpy().view(np.uint32), want[f].view(np.uint32)))
         return ok
 
@@ -121,6 +161,9 @@ def measure(args, torch, lcfir, batch, np, name, files, taps, dev):
         "items": (s_a, ib.step, args.steps, args.steps),
         "items_groups": (s_a, ib_g.step, args.steps, args.steps),
         "items_parts": (s_a, ib_p.step, args.steps, args.steps),
+        "tensors": (s_a, tb.step, args.steps, args.steps),
+        "tensors_copies": (s_a, copies_step, args.steps, args.steps),
+        "groups_again": (s_a, ib_2.step, args.steps, args.steps),
     }
     # pre-roll: untimed work until the clock has settled, every arrangement warm
     t0 = time.perf_counter()
@@ -152,12 +195,21 @@ def measure(args, torch, lcfir, batch, np, name, files, taps, dev):
         out[k] = {"step_ms_median": round(med, 4), "step_ms_min": round(min(v), 4), "step_ms_max": round(max(v), 4),
                   "host_step_ms_median": round(statistics.median(host[k]), 4),
                   "gsamples_per_s": round(samples / med / 1e6, 3)}
+    # the floor of this run's comparisons: the same step on two item sets, at
+    # two places of the alternation
+    g, g2 = out["items_groups"]["step_ms_median"], out["groups_again"]["step_ms_median"]
+    floor = abs(g - g2)
+    tens, cop = out["tensors"]["step_ms_median"], out["tensors_copies"]["step_ms_median"]
+    out["comparisons"] = {"floor_ms": round(floor, 4), "floor_rel": round(floor / min(g, g2), 4),
+                          "tensors_copies_minus_tensors_ms": round(cop - tens, 4),
+                          "tensors_copies_over_tensors": round(cop / tens, 3),
+                          "tensors_beyond_floor": bool(cop - tens > floor)}
     run_a.close()
     run_b.close()
     torch.cuda.synchronize()
-    ibe.close()
-    ibe_g.close()
-    ibe_p.close()
+    tb.close()
+    for be in (ibe, ibe_g, ibe_p, ibe_2, ibe_c):
+        be.close()
     flt.close()
     return out
 
@@ -203,11 +255,16 @@ def main():
               f"{r['fused_units']} fused units = {r['grid_rounds']} rounds of {r['cus']} CUs "
               f"({r['fused_units_parts']} under parts), "
               f"same bytes: {r['equal_per_file_calls']}")
-        for k in ("eager", "graphed", "items", "items_groups", "items_parts"):
+        for k in ("eager", "graphed", "items", "items_groups", "items_parts", "tensors", "tensors_copies",
+                  "groups_again"):
             v = r[k]
-            print(f"  {k:12s} {v['step_ms_median']:9.4f} ms/step (min {v['step_ms_min']:.4f}, max "
+            print(f"  {k:14s} {v['step_ms_median']:9.4f} ms/step (min {v['step_ms_min']:.4f}, max "
                   f"{v['step_ms_max']:.4f}; host clock {v['host_step_ms_median']:.4f})  "
                   f"{v['gsamples_per_s']:8.3f} Gsamples/s")
+        c = r["comparisons"]
+        print(f"  floor (items_groups against groups_again): {c['floor_ms']:.4f} ms ({100 * c['floor_rel']:.1f} %); "
+              f"tensors_copies - tensors: {c['tensors_copies_minus_tensors_ms']:+.4f} ms, "
+              f"x{c['tensors_copies_over_tensors']:.2f} (beyond the floor: {c['tensors_beyond_floor']})")
     line = json.dumps({"items_rate": results})
     print(line)
     if args.out:
