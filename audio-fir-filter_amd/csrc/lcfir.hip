@@ -24,6 +24,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -813,6 +814,11 @@ int lcfir_ctx_create(int device, const double *taps, int32_t ntaps, lcfir_ctx **
     if (!taps) return fail(LCFIR_EINVAL, "taps is null");
     if (ntaps < 1 || (ntaps & 1) == 0)
         return fail(LCFIR_EINVAL, "ntaps must be odd and >= 1 (kernel length M+1), got %d", ntaps);
+    // the taps' value domain (include/lcfir.h): a NaN or Inf tap would meet the
+    // zero padding in the direct kernel (0 * Inf) and fill the FFT's pair tables
+    for (int32_t k = 0; k < ntaps; ++k)
+        if (!std::isfinite(taps[k]))
+            return fail(LCFIR_EINVAL, "taps[%d] is not finite (%g): every tap must be a finite double", k, taps[k]);
     int ndev = 0;
     LCFIR_HIP(hipGetDeviceCount(&ndev));
     if (device < 0 || device >= ndev)

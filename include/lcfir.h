@@ -44,6 +44,27 @@
  *     f64 fma, mul and add); nothing has an absolute floor.
  *   - Subnormal samples, outputs and peaks are honoured: nothing flushes to 0.
  *   - The f32 codec formats move bits (NaN payloads survive decode and encode).
+ *
+ * The taps' value domain (tests/test_gpu_tap_domain.py):
+ *   - Every tap must be a finite double.  lcfir_ctx_create returns LCFIR_EINVAL
+ *     for a NaN or +-Inf tap and names the first such index, before any device
+ *     call: the methods could not agree on one (the direct kernel multiplies a
+ *     channel edge's zero padding by it, 0 * Inf = NaN, where the reference's
+ *     shortened sums never reach it; the FFT's tables would be all NaN).
+ *   - Any finite taps are honoured: symmetric, antisymmetric, one-sided, all
+ *     zero (every output and peak 0).  Nothing assumes a low-cut's shape.
+ *   - Delays are exact.  A single unit tap h[k] = 1 gives y[n] = x[n + k - M/2]
+ *     bit for bit, and h[M/2 - d] = h[M/2 + d] = 0.5 gives (x[n-d] + x[n+d]) / 2
+ *     correctly rounded, for every method wherever the expected output is
+ *     not 0 (samples on the 16-bit grid; the FFT's f64 error, 2^-50 |h|_1 max|x|,
+ *     is far below half an f32 spacing there); the direct method's zeros are
+ *     exact, the FFT's within 1e-12.
+ *   - Scale invariance holds in the taps too: y(2^s h) = 2^s y(h) bit for bit
+ *     wherever both sides are normal f32, for every method, with the same
+ *     plan; no threshold on the taps is absolute.
+ *   - Taps symmetric up to an antisymmetric part of 2^-50 of their l1 norm run
+ *     the FFT's zero-phase form (lcfir_ctx_fft_info); anything above runs the
+ *     general table.
  */
 #ifndef LCFIR_H
 #define LCFIR_H

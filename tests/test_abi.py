@@ -57,6 +57,28 @@ def test_even_tap_count_rejected_without_device():
     assert not ctx.value
 
 
+@pytest.mark.parametrize("bad", [np.nan, np.inf, -np.inf])
+@pytest.mark.parametrize("ntaps,at", [(1, 0), (15, 0), (15, 7), (15, 14), (4001, 3999)])
+def test_non_finite_taps_rejected_without_device(bad, ntaps, at):
+    """The taps' value domain (include/lcfir.h): a NaN or +-Inf tap is
+    LCFIR_EINVAL before any device call, the message naming the first
+    offending index (a second bad tap behind it does not change it)."""
+    lib = lcfir.load()
+    taps = np.linspace(-1.0, 1.0, ntaps) if ntaps > 1 else np.ones(1)
+    taps[at] = bad
+    if at < ntaps - 1:
+        taps[-1] = np.nan
+    ctx = ctypes.c_void_p()
+    rc = lib.lcfir_ctx_create(0, taps.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ntaps, ctypes.byref(ctx))
+    assert rc == lcfir.EINVAL
+    msg = lib.lcfir_last_error().decode()
+    assert f"taps[{at}]" in msg and "finite" in msg, msg
+    assert not ctx.value
+    with pytest.raises(lcfir.LcfirError, match=rf"taps\[{at}\]") as e:
+        lcfir.Filter(taps)
+    assert e.value.code == lcfir.EINVAL
+
+
 def test_null_arguments_rejected():
     lib = lcfir.load()
     assert lib.lcfir_ctx_create(0, None, 3, None) == lcfir.EINVAL
