@@ -331,4 +331,70 @@ __global__ __launch_bounds__(kItemThreads) void items_encode_scaled_kernel(const
     }
 }
 
+// encode_pcm_dither_kernel over every file at once.  ItemTile.first is the
+// tile's first interleaved sample of its file, so with frame0 = 0 a sample's
+// noise is keyed on its own file's channel and frame: the bytes of a file are
+// the per-file call's whatever the batch.  Tiles start a multiple of
+// kItemPcmTile samples into the payload, so a tile's quads (two per thread)
+// start on dwords exactly where the payload does; such a tile stores dwords
+// and its last count % 4 samples bytes, any other keeps the per-sample byte
+// store.  peak == nullptr: no rescale.
+template <int DITHER>
+__global__ __launch_bounds__(kItemThreads) void items_encode_dither_kernel(const float *__restrict__ y,
+                                                                           const ItemTile *__restrict__ tiles,
+                                                                           int64_t ntiles,
+                                                                           const ItemFile *__restrict__ files,
+                                                                           const ItemPcm *__restrict__ pcm,
+                                                                           const unsigned *__restrict__ peak,
+                                                                           int force, uint64_t seed,
+                                                                           uint8_t *__restrict__ out) {
+    constexpr int kQuads = kItemPcmLoads / 4; // quads per thread and tile
+    for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        const ItemTile tl = tiles[t];
+        const ItemFile fl = files[tl.file];
+        const ItemPcm io = pcm[tl.file];
+        const float pk = peak ? __uint_as_float(peak[tl.file]) : 0.0f;
+        const bool scale = (pk > 1.0f || force) && pk > 0.0f;
+        const double gain = scale ? 1.0 / (double)pk : 1.0;
+        const float *__restrict__ src = y + fl.off;
+        uint8_t *__restrict__ dst = out + io.byte_off;
+        int done = 0; // samples of the tile the dword path covers
+        if ((reinterpret_cast<uintptr_t>(dst + tl.first * io.f.bytes) & 3) == 0) {
+            const int vec = quad_vec(src, fl.stride, fl.nch);
+            const int nquad = tl.count >> 2;
+            float v[kQuads][4];
+            int64_t fr[kQuads][4];
+            int ch[kQuads][4];
+#pragma unroll
+            for (int u = 0; u < kQuads; ++u) {
+                const int q = (int)threadIdx.x + u * kItemThreads;
+                if (q < nquad) load_quad(src, fl.stride, fl.nch, vec, tl.first + 4 * q, v[u], fr[u], ch[u]);
+            }
+#pragma unroll
+            for (int u = 0; u < kQuads; ++u) {
+                const int q = (int)threadIdx.x + u * kItemThreads;
+                if (q < nquad) {
+                    uint32_t e[4];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const float s = scale ? scale_one(v[u][j], gain) : v[u][j];
+                        e[j] = encode_one_dither<DITHER>(s, io.f, seed, ch[u][j], (uint64_t)fr[u][j]);
+                    }
+                    store_quad(dst + (tl.first + 4 * q) * io.f.bytes, e, io.f);
+                }
+            }
+            done = nquad * 4;
+        }
+        for (int k = done + (int)threadIdx.x; k < tl.count; k += kItemThreads) {
+            const int64_t i = tl.first + k;
+            const int64_t fr = i / fl.nch;
+            const int ch = (int)(i - fr * fl.nch);
+            const float v = src[(int64_t)ch * fl.stride + fr];
+            const float s = scale ? scale_one(v, gain) : v;
+            store_bytes(dst + i * io.f.bytes, encode_one_dither<DITHER>(s, io.f, seed, ch, (uint64_t)fr), io.f.bytes,
+                        io.f.big_endian);
+        }
+    }
+}
+
 } // namespace lcfir

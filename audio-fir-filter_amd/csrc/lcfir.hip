@@ -1475,6 +1475,44 @@ int lcfir_encode_pcm_scaled_dev(const float *d_in, int64_t in_stride, int32_t nc
     return LCFIR_OK;
 }
 
+int lcfir_dither_tpdf(uint64_t seed, int32_t ch, int64_t frame0, int64_t count, double *d) {
+    if (ch < 0) return fail(LCFIR_EINVAL, "negative channel %d", ch);
+    if (frame0 < 0 || count < 0) return fail(LCFIR_EINVAL, "negative frame0 or count");
+    if (frame0 > INT64_MAX - count) return fail(LCFIR_EINVAL, "frame0 + count overflows int64");
+    if (count > 0 && !d) return fail(LCFIR_EINVAL, "d is null");
+    for (int64_t i = 0; i < count; ++i) d[i] = lcfir::dither_tpdf(seed, ch, (uint64_t)(frame0 + i));
+    return LCFIR_OK;
+}
+
+static int dither_mode(int dither) {
+    if (dither != LCFIR_DITHER_NONE && dither != LCFIR_DITHER_TPDF)
+        return fail(LCFIR_EINVAL, "unknown dither mode %d", dither);
+    return LCFIR_OK;
+}
+
+int lcfir_encode_pcm_dither_dev(const float *d_in, int64_t in_stride, int32_t nch, int64_t frames, int format,
+                                const float *d_peak, int32_t npeak, int force, int dither, uint64_t seed,
+                                int64_t frame0, void *d_out, void *stream) {
+    lcfir::PcmFormat f;
+    if (!pcm_format(format, f)) return fail(LCFIR_EINVAL, "unknown PCM format %d", format);
+    if (const int rc = dither_mode(dither)) return rc;
+    if (nch < 0 || frames < 0 || npeak < 0) return fail(LCFIR_EINVAL, "negative size");
+    if (frame0 < 0) return fail(LCFIR_EINVAL, "negative frame0");
+    if (frame0 > INT64_MAX - frames) return fail(LCFIR_EINVAL, "frame0 + frames overflows int64");
+    if (nch == 0 || frames == 0) return LCFIR_OK;
+    if (!d_in || !d_out || (npeak > 0 && !d_peak)) return fail(LCFIR_EINVAL, "null argument");
+    if (nch > 1 && in_stride < frames) return fail(LCFIR_EINVAL, "channel stride < frames");
+    if (frames > INT64_MAX / 4 / nch) return fail(LCFIR_EINVAL, "frames * nch too large");
+    const int blocks = stream_blocks(frames * nch, 256 * 8);
+    const auto kernel = dither == LCFIR_DITHER_TPDF ? lcfir::encode_pcm_dither_kernel<lcfir::kDitherTpdf>
+                                                    : lcfir::encode_pcm_dither_kernel<lcfir::kDitherNone>;
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), d_in, in_stride,
+                       (int)nch, frames, f, reinterpret_cast<const unsigned *>(d_peak), (int)npeak, force ? 1 : 0,
+                       seed, (uint64_t)frame0, reinterpret_cast<uint8_t *>(d_out));
+    LCFIR_HIP(hipGetLastError());
+    return LCFIR_OK;
+}
+
 // ---- item sets ---------------------------------------------------------------
 constexpr int32_t kItemMaxRows = 65535; // rows of one launch (the kernels' grid.y)
 
@@ -2018,6 +2056,29 @@ int lcfir_items_encode_pcm_scaled_dev(lcfir_items *it, const float *d_peak, int 
     hipLaunchKernelGGL(lcfir::items_encode_scaled_kernel, dim3(items_blocks(it->n_pcm_tiles)),
                        dim3(lcfir::kItemThreads), 0, s, it->d_out, it->d_pcm_tiles, it->n_pcm_tiles, it->d_files,
                        it->d_pcm, reinterpret_cast<const unsigned *>(d_peak), force ? 1 : 0,
+                       reinterpret_cast<uint8_t *>(d_bytes));
+    LCFIR_HIP(hipGetLastError());
+    return LCFIR_OK;
+}
+
+int lcfir_items_encode_pcm_dither_dev(lcfir_items *it, const float *d_peak, int force, int dither, uint64_t seed,
+                                      void *d_bytes, const int64_t *byte_offset, const int32_t *format,
+                                      void *stream) {
+    if (!it) return fail(LCFIR_EINVAL, "items is null");
+    if (const int rc = dither_mode(dither)) return rc;
+    if (it->n_pcm_tiles == 0) return LCFIR_OK;
+    if (!d_bytes || !byte_offset || !format) return fail(LCFIR_EINVAL, "null argument");
+    DeviceGuard g(it->device);
+    if (!g.ok) return fail(LCFIR_EDEVICE, "hipSetDevice(%d) failed", it->device);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int rc = items_pcm_table(it, byte_offset, format, s);
+    if (rc) return rc;
+    items_note_stream(it, s);
+    const auto kernel = dither == LCFIR_DITHER_TPDF ? lcfir::items_encode_dither_kernel<lcfir::kDitherTpdf>
+                                                    : lcfir::items_encode_dither_kernel<lcfir::kDitherNone>;
+    hipLaunchKernelGGL(kernel, dim3(items_blocks(it->n_pcm_tiles)), dim3(lcfir::kItemThreads), 0, s, it->d_out,
+                       it->d_pcm_tiles, it->n_pcm_tiles, it->d_files, it->d_pcm,
+                       reinterpret_cast<const unsigned *>(d_peak), force ? 1 : 0, seed,
                        reinterpret_cast<uint8_t *>(d_bytes));
     LCFIR_HIP(hipGetLastError());
     return LCFIR_OK;

@@ -9,7 +9,9 @@
 // covers a channel), -O/--overwrite, -h/--help.  Extensions: --method
 // auto|direct|fft, --devices LIST (default: every visible GPU) / --device N,
 // --info (print the parsed format, no GPU), --plan (print the file-to-GPU
-// dealing, no GPU).
+// dealing, no GPU), --dither / --dither-seed N (TPDF dither in the integer
+// encode; keyed on the file's own channel and frame, so a file's output does
+// not depend on its place in a batch or on the dealing).
 //
 // A batch (scenario 2, main.cp:132-147) is dealt round-robin over the
 // devices, one file per GPU at a time (BASELINE.json north_star: "shard one
@@ -72,6 +74,8 @@ struct Options {
     std::vector<int> devices; // empty: every visible device
     int readers = 1;          // file-reader threads
     bool plan = false;
+    bool dither = false;
+    uint64_t dither_seed = 0;
     std::vector<std::string> paths;
 };
 
@@ -115,6 +119,10 @@ Options:
   --device arg                  one GPU (= --devices arg)
   --readers arg (=1)            File-reader threads (files read in parallel;
                                 more than one measured slower on one GPU).
+  --dither                      Add TPDF dither (+-1 LSB, seed 0) before rounding
+                                to an integer format; float files are unchanged.
+  --dither-seed arg             Seed of the dither noise (implies --dither). The
+                                noise depends on seed, channel and frame only.
   --plan                        Print which GPU stage each file goes to and exit.
   --info                        Print each input's format and exit.
   --timing                      Print per-file read/GPU/write times and the
@@ -158,6 +166,18 @@ Options parse(int argc, char **argv) {
         else if (a == "--device") o.devices = {std::stoi(val(a))};
         else if (a == "--devices") o.devices = parse_devices(val(a));
         else if (a == "--plan") o.plan = true;
+        else if (a == "--dither") o.dither = true;
+        else if (a == "--dither-seed") {
+            const std::string v = val(a);
+            if (v.empty() || v.find_first_not_of("0123456789") != std::string::npos || v.size() > 20)
+                throw UsageError("bad --dither-seed value: " + v);
+            try {
+                o.dither_seed = std::stoull(v);
+            } catch (const std::out_of_range &) {
+                throw UsageError("bad --dither-seed value: " + v);
+            }
+            o.dither = true;
+        }
         else if (a == "--readers") {
             const std::string v = val(a);
             if (v.empty() || v.find_first_not_of("0123456789") != std::string::npos || v.size() > 3)
@@ -356,9 +376,16 @@ void enqueue_file(Slot &s, Job &j, FilterSet &filters, PinnedPool &pool, const O
     check(lcfir_filter_channels_dev(flt.ctx, d_x, n, nch, n, d_y, n, d_peak, s.stream), "filter");
     // the normalize decision and gain ride in the encode pass, which reads every
     // sample anyway: no separate rescale pass over the f32 planes
-    check(lcfir_encode_pcm_scaled_dev(d_y, n, nch, n, f.pcm_format, d_peak, nch, o.normalize ? 1 : 0, d_raw,
-                                      s.stream),
-          "encode");
+    if (o.dither)
+        // frame 0 of the file and the run's one seed: the same bytes wherever
+        // the file stands in the batch and whichever GPU it is dealt to
+        check(lcfir_encode_pcm_dither_dev(d_y, n, nch, n, f.pcm_format, d_peak, nch, o.normalize ? 1 : 0,
+                                          LCFIR_DITHER_TPDF, o.dither_seed, 0, d_raw, s.stream),
+              "encode");
+    else
+        check(lcfir_encode_pcm_scaled_dev(d_y, n, nch, n, f.pcm_format, d_peak, nch, o.normalize ? 1 : 0, d_raw,
+                                          s.stream),
+              "encode");
     check(lcfir_memcpy_d2h_async(f.data + f.data_offset, d_raw, f.data_bytes, s.stream), "d2h");
     check(lcfir_memcpy_d2h_async(s.peaks_host.get(), d_peak, sizeof(float) * (size_t)nch, s.stream),
           "d2h");

@@ -107,6 +107,9 @@ _SIGNATURES = {
     "lcfir_encode_pcm_dev": ([_vp, _c_i64, _c_i32, _c_i64, _c_int, _vp, _vp], _c_int),
     "lcfir_encode_pcm_scaled_dev": ([_vp, _c_i64, _c_i32, _c_i64, _c_int, _vp, _c_i32, _c_int, _vp, _vp],
                                     _c_int),
+    "lcfir_dither_tpdf": ([ctypes.c_uint64, _c_i32, _c_i64, _c_i64, _vp], _c_int),
+    "lcfir_encode_pcm_dither_dev": ([_vp, _c_i64, _c_i32, _c_i64, _c_int, _vp, _c_i32, _c_int, _c_int,
+                                     ctypes.c_uint64, _c_i64, _vp, _vp], _c_int),
     "lcfir_items_plan": ([_c_i64, _c_i32, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(_c_i32), _vp, _vp, _vp,
                           ctypes.POINTER(_c_i32), ctypes.POINTER(_c_i64), ctypes.POINTER(_c_i64)], _c_int),
     "lcfir_items_create": ([_ctxp, _vp, _vp, _c_i32, ctypes.POINTER(_vp)], _c_int),
@@ -122,6 +125,7 @@ _SIGNATURES = {
     "lcfir_items_normalize_dev": ([_vp, _vp, _c_int, _vp], _c_int),
     "lcfir_items_decode_pcm_dev": ([_vp, _vp, _vp, _vp, _vp], _c_int),
     "lcfir_items_encode_pcm_scaled_dev": ([_vp, _vp, _c_int, _vp, _vp, _vp, _vp], _c_int),
+    "lcfir_items_encode_pcm_dither_dev": ([_vp, _vp, _c_int, _c_int, ctypes.c_uint64, _vp, _vp, _vp, _vp], _c_int),
     "lcfir_items_gather_dev": ([_vp, _vp, _vp, _vp], _c_int),
     "lcfir_items_scatter_scaled_dev": ([_vp, _vp, _c_int, _vp, _vp, _vp], _c_int),
     "lcfir_dev_malloc": ([_c_int, ctypes.c_size_t, ctypes.POINTER(_vp)], _c_int),
@@ -519,6 +523,16 @@ class ItemSet:
         _check(load().lcfir_items_encode_pcm_scaled_dev(self._h, _ptr(d_peak), 1 if force else 0, _ptr(d_bytes),
                                                         off.ctypes.data, fmt.ctypes.data, stream or None))
 
+    def encode_pcm_dither_dev(self, d_peak, force: bool, dither: str, seed: int, d_bytes, byte_offset, formats,
+                              stream=0):
+        """encode_pcm_scaled_dev with the dither option ("none" / "tpdf"): each
+        file's noise is keyed on its own channel and frame, so its bytes are
+        the per-file encode_pcm_dither_dev's; d_peak None: no rescale."""
+        off, fmt = self._pcm_args(byte_offset, formats)
+        _check(load().lcfir_items_encode_pcm_dither_dev(
+            self._h, _ptr(d_peak) if d_peak is not None else None, 1 if force else 0, _dither_mode(dither),
+            int(seed) & _U64, _ptr(d_bytes), off.ctypes.data, fmt.ctypes.data, stream or None))
+
     def _span_args(self, ptrs, strides):
         p = np.ascontiguousarray(np.asarray([int(x or 0) for x in ptrs], dtype=np.uint64))
         st = np.ascontiguousarray(np.asarray(strides, dtype=np.int64).reshape(-1))
@@ -771,3 +785,32 @@ def encode_pcm_scaled_dev(d_in, in_stride: int, nch: int, frames: int, fmt: str,
     _check(load().lcfir_encode_pcm_scaled_dev(_ptr(d_in), in_stride, nch, frames, PCM_FORMATS[fmt],
                                               _ptr(d_peak), npeak, 1 if force else 0, _ptr(d_out),
                                               stream or None))
+
+
+# -- TPDF dither (include/lcfir.h, LCFIR_DITHER_*) ------------------------------
+DITHER_MODES = {"none": 0, "tpdf": 1}
+_U64 = (1 << 64) - 1
+
+
+def _dither_mode(dither) -> int:
+    """"none" / "tpdf"; an integer goes to the library as it is (which checks it)."""
+    return DITHER_MODES[dither] if isinstance(dither, str) else int(dither)
+
+
+def dither_tpdf(seed: int, ch: int, frame0: int, count: int) -> np.ndarray:
+    """lcfir_dither_tpdf: the noise of (seed, ch, frame0 + i), i < count, in LSB (host only)."""
+    lib = load()
+    d = np.empty(max(int(count), 0), np.float64)
+    _check(lib.lcfir_dither_tpdf(int(seed) & _U64, ch, frame0, count, d.ctypes.data if d.size else None))
+    return d
+
+
+def encode_pcm_dither_dev(d_in, in_stride: int, nch: int, frames: int, fmt: str, d_peak, npeak: int, force: bool,
+                          dither: str, seed: int, frame0: int, d_out, stream=0):
+    """encode_pcm_scaled_dev with the dither option: dither "none" (the same
+    bytes) or "tpdf"; frame0 is the file's frame index of the call's first
+    frame.  d_peak may be None when npeak is 0."""
+    _check(load().lcfir_encode_pcm_dither_dev(_ptr(d_in), in_stride, nch, frames, PCM_FORMATS[fmt],
+                                              _ptr(d_peak) if d_peak is not None else None, npeak,
+                                              1 if force else 0, _dither_mode(dither), int(seed) & _U64, frame0,
+                                              _ptr(d_out), stream or None))

@@ -374,6 +374,54 @@ int lcfir_encode_pcm_scaled_dev(const float *d_in, int64_t in_stride, int32_t nc
                                 int format, const float *d_peak, int32_t npeak, int force,
                                 void *d_out, void *stream);
 
+/* ---- TPDF dither for the integer encode (opt-in) ------------------------- */
+/* Plain rounding to 16 or 24 bits leaves an error correlated with the signal:
+ * what a low-cut leaves of room tone or a fade, a few LSB, comes out as
+ * harmonic distortion or as digital silence.  Triangular noise of +-1 LSB
+ * added before the rounding makes the error's mean and variance independent
+ * of the signal.  The noise is a pure function of (seed, channel, absolute
+ * frame index of the file), never of a generator's state, so a file's bytes
+ * do not depend on how its frames were cut into calls, devices or item-set
+ * rows.  All integer arithmetic is modulo 2^64:
+ *
+ *   s = seed ^ ((uint64)(ch + 1) * 0xD1B54A32D192ED03)
+ *   z = s + (uint64)frame * 0x9E3779B97F4A7C15
+ *   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9
+ *   z = (z ^ (z >> 27)) * 0x94D049BB133111EB
+ *   z =  z ^ (z >> 31)
+ *   d = ((double)(z >> 32) - (double)(z & 0xFFFFFFFF)) * 2^-32
+ *
+ * d lies in (-1, 1) LSB, triangular, and every step is exact in f64.  The
+ * dithered encode of a float v for a b-bit integer format is
+ *
+ *   q = rint((double)v * 2^(b-1) + d)
+ *
+ * (the product is exact, so the add is the only rounding), then the plain
+ * encode's clamp to [-2^(b-1), 2^(b-1) - 1] and its NaN -> 0.  The float32
+ * formats pass their bits through, dither or not.  With a rescale folded in,
+ * v is first (float)((double)v * (1.0 / (double)peak)), as in
+ * lcfir_encode_pcm_scaled_dev. */
+#define LCFIR_DITHER_NONE 0
+#define LCFIR_DITHER_TPDF 1
+
+/* Pure host function, no device: d[i] = the noise of (seed, ch, frame0 + i),
+ * in LSB, i in [0, count).  LCFIR_EINVAL: ch, frame0 or count negative,
+ * frame0 + count overflowing int64, d NULL with count > 0. */
+int lcfir_dither_tpdf(uint64_t seed, int32_t ch, int64_t frame0, int64_t count, double *d);
+/* lcfir_encode_pcm_scaled_dev with the dither option.  frame0 is the absolute
+ * index, within its file, of the first frame the call encodes: frame i of the
+ * call takes the noise of frame0 + i, so a file encoded in ranges equals the
+ * file encoded whole.  d_peak may be NULL when npeak is 0 (no rescale).  With
+ * LCFIR_DITHER_NONE the output is lcfir_encode_pcm_scaled_dev's, byte for
+ * byte (seed and frame0 are checked and otherwise unused).  LCFIR_EINVAL: an
+ * unknown dither mode, a negative frame0, frame0 + frames overflowing int64;
+ * otherwise lcfir_encode_pcm_scaled_dev's argument rules.  Where d_out is
+ * 4-byte aligned the samples are stored as whole dwords, four samples a lane
+ * (all but the buffer's last frames * nch % 4); any d_out is accepted. */
+int lcfir_encode_pcm_dither_dev(const float *d_in, int64_t in_stride, int32_t nch, int64_t frames,
+                                int format, const float *d_peak, int32_t npeak, int force,
+                                int dither, uint64_t seed, int64_t frame0, void *d_out, void *stream);
+
 /* ---- item sets: a batch of files of different lengths in few launches ---- */
 /* The reference's batch scenario (main.cp:132-147) filters many files one
  * after another.  Every entry point above takes channels that share one
@@ -543,6 +591,16 @@ int lcfir_items_decode_pcm_dev(lcfir_items *items, const void *d_bytes, const in
                                const int32_t *format, void *stream);
 int lcfir_items_encode_pcm_scaled_dev(lcfir_items *items, const float *d_peak, int force, void *d_bytes,
                                       const int64_t *byte_offset, const int32_t *format, void *stream);
+/* lcfir_items_encode_pcm_scaled_dev with the dither option, one launch: every
+ * file's noise is keyed on its own channel and frame index (frame0 = 0) with
+ * the one seed, so file f's bytes are those of lcfir_encode_pcm_dither_dev on
+ * that file alone (npeak = 1, its own slot), whatever else is in the batch.
+ * d_peak may be NULL (no file is rescaled).  LCFIR_EINVAL for an unknown
+ * dither mode; like the two calls above it cannot be captured into a HIP
+ * graph. */
+int lcfir_items_encode_pcm_dither_dev(lcfir_items *items, const float *d_peak, int force, int dither,
+                                      uint64_t seed, void *d_bytes, const int64_t *byte_offset,
+                                      const int32_t *format, void *stream);
 /* The way in and out for files that already sit in device memory of the
  * caller's (torch tensors, say), one launch each whatever the file count.
  * d_src / d_dst and the strides are host arrays of nfiles entries, copied
