@@ -40,6 +40,80 @@
 #include "items.hpp"
 #include "peak_scale.hpp"
 
+namespace {
+
+thread_local std::string g_err;
+
+int fail(int code, const char *fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    g_err = buf;
+    return code;
+}
+
+#define LCFIR_HIP(expr)                                                                          \
+    do {                                                                                         \
+        hipError_t e_ = (expr);                                                                  \
+        if (e_ != hipSuccess)                                                                    \
+            return fail(LCFIR_EDEVICE, "%s failed: %s", #expr, hipGetErrorString(e_));           \
+    } while (0)
+
+// A per-call table of an item set (one T per file): filled into the next of
+// kSlots page-locked slots and copied to the device table `d` in stream order.
+// A slot is rewritten only once the copy that read it is done (its event).
+// `what` names the table in the allocation errors.
+template <class T, int kSlots>
+struct ItemRing {
+    const char *what;
+    size_t bytes = 0;
+    T *d = nullptr;
+    T *h[kSlots] = {};
+    hipEvent_t done[kSlots] = {};
+    bool pending[kSlots] = {};
+    int next = 0;
+    // device table, slots and events for nfiles entries (what exists already stays)
+    int ensure(int32_t nfiles) {
+        bytes = sizeof(T) * (size_t)nfiles;
+        if (!d && hipMalloc(reinterpret_cast<void **>(&d), bytes) != hipSuccess) {
+            d = nullptr;
+            return fail(LCFIR_ENOMEM, "hipMalloc for the %s table failed", what);
+        }
+        for (int k = 0; k < kSlots; ++k) {
+            if (!h[k] && hipHostMalloc(reinterpret_cast<void **>(&h[k]), bytes, hipHostMallocDefault) != hipSuccess) {
+                h[k] = nullptr;
+                return fail(LCFIR_ENOMEM, "hipHostMalloc for the %s table failed", what);
+            }
+            if (!done[k]) LCFIR_HIP(hipEventCreateWithFlags(&done[k], hipEventDisableTiming));
+        }
+        return LCFIR_OK;
+    }
+    // fill(slot) writes the call's table (nonzero: its error, nothing queued); the copy goes on s
+    template <class Fill>
+    int push(Fill fill, hipStream_t s) {
+        const int k = next;
+        if (pending[k]) LCFIR_HIP(hipEventSynchronize(done[k]));
+        pending[k] = false;
+        if (const int rc = fill(h[k])) return rc;
+        LCFIR_HIP(hipMemcpyAsync(d, h[k], bytes, hipMemcpyHostToDevice, s));
+        LCFIR_HIP(hipEventRecord(done[k], s));
+        pending[k] = true;
+        next = (k + 1) % kSlots;
+        return LCFIR_OK;
+    }
+    void release() {
+        if (d) (void)hipFree(d);
+        for (int k = 0; k < kSlots; ++k) {
+            if (h[k]) (void)hipHostFree(h[k]);
+            if (done[k]) (void)hipEventDestroy(done[k]);
+        }
+    }
+};
+
+} // namespace
+
 struct lcfir_ctx {
     int device = 0;
     int32_t ntaps = 0;
@@ -107,48 +181,18 @@ struct lcfir_items {
     lcfir::FftItemUnit *d_units = nullptr;
     int64_t n_units = 0, unit_B = 0, max_n = 0;
     std::atomic<int> fusion{LCFIR_ITEMS_FUSION_GROUPS};
-    // The codec calls' per-call table (payload offset and format per file):
-    // filled into a page-locked slot, copied to d_pcm in stream order.  A slot
-    // is rewritten only once the copy that read it is done (its event).
-    static constexpr int kPcmSlots = 4;
-    lcfir::ItemPcm *d_pcm = nullptr;
-    lcfir::ItemPcm *h_pcm[kPcmSlots] = {};
-    hipEvent_t pcm_done[kPcmSlots] = {};
-    bool pcm_pending[kPcmSlots] = {};
-    int pcm_next = 0;
+    // The codec calls' per-call table (payload offset and format per file),
+    // allocated at create.
+    ItemRing<lcfir::ItemPcm, 4> pcm{"codec"};
     // The tensor calls' per-call table (lcfir_items_gather_dev,
-    // _scatter_scaled_dev: pointer and stride per file), by the same route.
-    // Device table, slots and events are allocated at the first such call.
-    static constexpr int kSpanSlots = 2;
-    lcfir::ItemSpan *d_span = nullptr;
-    lcfir::ItemSpan *h_span[kSpanSlots] = {};
-    hipEvent_t span_done[kSpanSlots] = {};
-    bool span_pending[kSpanSlots] = {};
-    int span_next = 0;
+    // _scatter_scaled_dev: pointer and stride per file), allocated at the
+    // first such call.
+    ItemRing<lcfir::ItemSpan, 2> span{"span"};
     std::mutex mu;
     std::vector<hipStream_t> used; // every stream a call on this item set went to
 };
 
 namespace {
-
-thread_local std::string g_err;
-
-int fail(int code, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return code;
-}
-
-#define LCFIR_HIP(expr)                                                                          \
-    do {                                                                                         \
-        hipError_t e_ = (expr);                                                                  \
-        if (e_ != hipSuccess)                                                                    \
-            return fail(LCFIR_EDEVICE, "%s failed: %s", #expr, hipGetErrorString(e_));           \
-    } while (0)
 
 struct DeviceGuard {
     int prev = -1;
@@ -230,6 +274,31 @@ void note_stream(lcfir_ctx *ctx, hipStream_t s) {
     for (hipStream_t u : ctx->used)
         if (u == s) return;
     ctx->used.push_back(s);
+}
+
+// The same for an item set (lcfir_items_destroy waits for it).
+void items_note_stream(lcfir_items *it, hipStream_t s) {
+    std::lock_guard<std::mutex> lk(it->mu);
+    for (hipStream_t u : it->used)
+        if (u == s) return;
+    it->used.push_back(s);
+}
+
+// One tile-walking pass (items.hpp) over ntiles tiles on s: a few blocks per
+// CU, grid-stride beyond
+template <class Kernel, class... Args>
+int items_pass(lcfir_items *it, hipStream_t s, Kernel kernel, int64_t ntiles, Args... args) {
+    items_note_stream(it, s);
+    const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>(ntiles, (int64_t)device_cus() * 8));
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(lcfir::kItemThreads), 0, s, args...);
+    LCFIR_HIP(hipGetLastError());
+    return LCFIR_OK;
+}
+
+// Is a HIP graph being captured on s?
+bool stream_capturing(hipStream_t s) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    return hipStreamIsCapturing(s, &cs) == hipSuccess && cs == hipStreamCaptureStatusActive;
 }
 
 // The partial-sum scratch of stream s, at least `need` doubles, allocated and
@@ -1644,11 +1713,13 @@ static void items_unit_files_fill(int64_t B, const int64_t *n, const int32_t *nc
     }
 }
 
-int lcfir_items_unit_files(int64_t B, int32_t nfiles, const int64_t *n, const int32_t *nch, int64_t *nunits,
-                           int32_t *file, int64_t cap) {
+// lcfir_items_unit_table / _unit_files up to the fill: the plan over unit = B,
+// the entry count into *nunits, and the check of the output array `out`
+// (`name` in the error) against it
+static int items_unit_plan(int64_t B, int32_t nfiles, const int64_t *n, const int32_t *nch, int64_t *nunits,
+                           const void *out, const char *name, int64_t cap, ItemsPlan &pl) {
     if (!nunits) return fail(LCFIR_EINVAL, "nunits is null");
     *nunits = 0;
-    ItemsPlan pl;
     int rc = items_plan(B, nfiles, n, nch, pl);
     if (rc) return rc;
     int64_t total = 0;
@@ -1656,38 +1727,26 @@ int lcfir_items_unit_files(int64_t B, int32_t nfiles, const int64_t *n, const in
     if (rc) return rc;
     *nunits = total;
     if (cap < total) return fail(LCFIR_EINVAL, "%lld entries do not fit cap = %lld", (long long)total, (long long)cap);
-    if (total > 0 && !file) return fail(LCFIR_EINVAL, "file is null");
+    if (total > 0 && !out) return fail(LCFIR_EINVAL, "%s is null", name);
+    return LCFIR_OK;
+}
+
+int lcfir_items_unit_files(int64_t B, int32_t nfiles, const int64_t *n, const int32_t *nch, int64_t *nunits,
+                           int32_t *file, int64_t cap) {
+    ItemsPlan pl;
+    const int rc = items_unit_plan(B, nfiles, n, nch, nunits, file, "file", cap, pl);
+    if (rc) return rc;
     items_unit_files_fill(B, n, nch, pl, file);
     return LCFIR_OK;
 }
 
 int lcfir_items_unit_table(int64_t B, int32_t nfiles, const int64_t *n, const int32_t *nch, int64_t *nunits,
                            lcfir_item_unit *entries, int64_t cap) {
-    if (!nunits) return fail(LCFIR_EINVAL, "nunits is null");
-    *nunits = 0;
     ItemsPlan pl;
-    int rc = items_plan(B, nfiles, n, nch, pl);
+    const int rc = items_unit_plan(B, nfiles, n, nch, nunits, entries, "entries", cap, pl);
     if (rc) return rc;
-    int64_t total = 0;
-    rc = items_unit_count(B, n, nch, pl, total);
-    if (rc) return rc;
-    *nunits = total;
-    if (cap < total) return fail(LCFIR_EINVAL, "%lld entries do not fit cap = %lld", (long long)total, (long long)cap);
-    if (total > 0 && !entries) return fail(LCFIR_EINVAL, "entries is null");
     items_unit_fill(B, n, nch, pl, reinterpret_cast<lcfir::FftItemUnit *>(entries));
     return LCFIR_OK;
-}
-
-static void items_note_stream(lcfir_items *it, hipStream_t s) {
-    std::lock_guard<std::mutex> lk(it->mu);
-    for (hipStream_t u : it->used)
-        if (u == s) return;
-    it->used.push_back(s);
-}
-
-// blocks of a tile-walking pass (items.hpp): a few per CU, grid-stride beyond
-static unsigned items_blocks(int64_t ntiles) {
-    return (unsigned)std::max<int64_t>(1, std::min<int64_t>(ntiles, (int64_t)device_cus() * 8));
 }
 
 // a device copy of a host table, queued on s (the caller waits for s before src dies)
@@ -1788,16 +1847,8 @@ int lcfir_items_create(lcfir_ctx *ctx, const int64_t *n, const int32_t *nch, int
             r = items_upload(reinterpret_cast<void **>(&it->d_units), units.data(),
                              units.size() * sizeof(lcfir::FftItemUnit), up);
         if (r) return r;
-        if (nfiles > 0) {
-            const size_t tb = sizeof(lcfir::ItemPcm) * (size_t)nfiles;
-            if (hipMalloc(reinterpret_cast<void **>(&it->d_pcm), tb) != hipSuccess)
-                return fail(LCFIR_ENOMEM, "hipMalloc for the codec table failed");
-            for (int k = 0; k < lcfir_items::kPcmSlots; ++k) {
-                if (hipHostMalloc(reinterpret_cast<void **>(&it->h_pcm[k]), tb, hipHostMallocDefault) != hipSuccess)
-                    return fail(LCFIR_ENOMEM, "hipHostMalloc for the codec table failed");
-                LCFIR_HIP(hipEventCreateWithFlags(&it->pcm_done[k], hipEventDisableTiming));
-            }
-        }
+        if (nfiles > 0) r = it->pcm.ensure(nfiles);
+        if (r) return r;
         LCFIR_HIP(hipStreamSynchronize(up));
         return LCFIR_OK;
     };
@@ -1820,18 +1871,11 @@ int lcfir_items_destroy(lcfir_items *it) {
     if (!it) return LCFIR_OK;
     DeviceGuard g(it->device);
     for (hipStream_t s : it->used) (void)hipStreamSynchronize(s);
-    void *bufs[] = {it->d_in, it->d_out, it->d_row_tiles, it->d_pcm_tiles, it->d_files, it->d_pcm, it->d_units};
+    void *bufs[] = {it->d_in, it->d_out, it->d_row_tiles, it->d_pcm_tiles, it->d_files, it->d_units};
     for (void *p : bufs)
         if (p) (void)hipFree(p);
-    for (int k = 0; k < lcfir_items::kPcmSlots; ++k) {
-        if (it->h_pcm[k]) (void)hipHostFree(it->h_pcm[k]);
-        if (it->pcm_done[k]) (void)hipEventDestroy(it->pcm_done[k]);
-    }
-    if (it->d_span) (void)hipFree(it->d_span);
-    for (int k = 0; k < lcfir_items::kSpanSlots; ++k) {
-        if (it->h_span[k]) (void)hipHostFree(it->h_span[k]);
-        if (it->span_done[k]) (void)hipEventDestroy(it->span_done[k]);
-    }
+    it->pcm.release();
+    it->span.release();
     delete it;
     return LCFIR_OK;
 }
@@ -1912,8 +1956,7 @@ int lcfir_items_filter_launches(lcfir_items *it, int32_t *filter_launches, int64
 static int items_filter_fused(lcfir_items *it, hipStream_t s) {
     lcfir_ctx *ctx = it->ctx;
     note_stream(ctx, s);
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs == hipStreamCaptureStatusActive) {
+    if (stream_capturing(s)) {
         std::lock_guard<std::mutex> lk(ctx->fft_mu);
         ctx->plan_captured = true;
     }
@@ -1974,12 +2017,9 @@ int lcfir_items_filter_dev(lcfir_items *it, float *d_peak, void *stream) {
         const int rc = run_filter(it->ctx, p, l.rows, s);
         if (rc) return rc;
     }
-    if (d_peak && it->n_row_tiles > 0) {
-        hipLaunchKernelGGL(lcfir::items_peak_kernel, dim3(items_blocks(it->n_row_tiles)), dim3(lcfir::kItemThreads),
-                           0, s, it->d_out, it->d_row_tiles, it->n_row_tiles, peak_bits(d_peak));
-        LCFIR_HIP(hipGetLastError());
-    }
-    return LCFIR_OK;
+    if (!d_peak || it->n_row_tiles == 0) return LCFIR_OK;
+    return items_pass(it, s, lcfir::items_peak_kernel, it->n_row_tiles, it->d_out, it->d_row_tiles, it->n_row_tiles,
+                      peak_bits(d_peak));
 }
 
 int lcfir_items_normalize_dev(lcfir_items *it, const float *d_peak, int force, void *stream) {
@@ -1988,40 +2028,31 @@ int lcfir_items_normalize_dev(lcfir_items *it, const float *d_peak, int force, v
     DeviceGuard g(it->device);
     if (!g.ok) return fail(LCFIR_EDEVICE, "hipSetDevice(%d) failed", it->device);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    items_note_stream(it, s);
-    hipLaunchKernelGGL(lcfir::items_normalize_kernel, dim3(items_blocks(it->n_row_tiles)),
-                       dim3(lcfir::kItemThreads), 0, s, it->d_out, it->d_row_tiles, it->n_row_tiles,
-                       reinterpret_cast<const unsigned *>(d_peak), force ? 1 : 0);
-    LCFIR_HIP(hipGetLastError());
-    return LCFIR_OK;
+    return items_pass(it, s, lcfir::items_normalize_kernel, it->n_row_tiles, it->d_out, it->d_row_tiles,
+                      it->n_row_tiles, reinterpret_cast<const unsigned *>(d_peak), force ? 1 : 0);
 }
 
 // Fill the next page-locked slot with the call's per-file table and queue its
-// copy to d_pcm on s.
+// copy to the codec table on s (ItemRing).
 static int items_pcm_table(lcfir_items *it, const int64_t *byte_offset, const int32_t *format, hipStream_t s) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs == hipStreamCaptureStatusActive)
+    if (stream_capturing(s))
         return fail(LCFIR_EINVAL, "the item set's codec calls cannot be captured into a HIP graph");
     std::lock_guard<std::mutex> lk(it->mu);
-    const int k = it->pcm_next;
-    if (it->pcm_pending[k]) LCFIR_HIP(hipEventSynchronize(it->pcm_done[k]));
-    it->pcm_pending[k] = false;
-    for (int32_t f = 0; f < it->nfiles; ++f) {
-        lcfir::ItemPcm e{0, {2, false, false}};
-        if (it->group[(size_t)f] >= 0) {
-            if (!pcm_format(format[f], e.f))
-                return fail(LCFIR_EINVAL, "file %d: unknown PCM format %d", f, format[f]);
-            if (byte_offset[f] < 0) return fail(LCFIR_EINVAL, "file %d: negative byte offset", f);
-            e.byte_off = byte_offset[f];
-        }
-        it->h_pcm[k][f] = e;
-    }
-    LCFIR_HIP(hipMemcpyAsync(it->d_pcm, it->h_pcm[k], sizeof(lcfir::ItemPcm) * (size_t)it->nfiles,
-                             hipMemcpyHostToDevice, s));
-    LCFIR_HIP(hipEventRecord(it->pcm_done[k], s));
-    it->pcm_pending[k] = true;
-    it->pcm_next = (k + 1) % lcfir_items::kPcmSlots;
-    return LCFIR_OK;
+    return it->pcm.push(
+        [&](lcfir::ItemPcm *slot) {
+            for (int32_t f = 0; f < it->nfiles; ++f) {
+                lcfir::ItemPcm e{0, {2, false, false}};
+                if (it->group[(size_t)f] >= 0) {
+                    if (!pcm_format(format[f], e.f))
+                        return fail(LCFIR_EINVAL, "file %d: unknown PCM format %d", f, format[f]);
+                    if (byte_offset[f] < 0) return fail(LCFIR_EINVAL, "file %d: negative byte offset", f);
+                    e.byte_off = byte_offset[f];
+                }
+                slot[f] = e;
+            }
+            return (int)LCFIR_OK;
+        },
+        s);
 }
 
 int lcfir_items_decode_pcm_dev(lcfir_items *it, const void *d_bytes, const int64_t *byte_offset,
@@ -2034,12 +2065,8 @@ int lcfir_items_decode_pcm_dev(lcfir_items *it, const void *d_bytes, const int64
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int rc = items_pcm_table(it, byte_offset, format, s);
     if (rc) return rc;
-    items_note_stream(it, s);
-    hipLaunchKernelGGL(lcfir::items_decode_kernel, dim3(items_blocks(it->n_pcm_tiles)), dim3(lcfir::kItemThreads),
-                       0, s, reinterpret_cast<const uint8_t *>(d_bytes), it->d_pcm_tiles, it->n_pcm_tiles,
-                       it->d_files, it->d_pcm, it->d_in);
-    LCFIR_HIP(hipGetLastError());
-    return LCFIR_OK;
+    return items_pass(it, s, lcfir::items_decode_kernel, it->n_pcm_tiles, reinterpret_cast<const uint8_t *>(d_bytes),
+                      it->d_pcm_tiles, it->n_pcm_tiles, it->d_files, it->pcm.d, it->d_in);
 }
 
 int lcfir_items_encode_pcm_scaled_dev(lcfir_items *it, const float *d_peak, int force, void *d_bytes,
@@ -2052,13 +2079,9 @@ int lcfir_items_encode_pcm_scaled_dev(lcfir_items *it, const float *d_peak, int 
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int rc = items_pcm_table(it, byte_offset, format, s);
     if (rc) return rc;
-    items_note_stream(it, s);
-    hipLaunchKernelGGL(lcfir::items_encode_scaled_kernel, dim3(items_blocks(it->n_pcm_tiles)),
-                       dim3(lcfir::kItemThreads), 0, s, it->d_out, it->d_pcm_tiles, it->n_pcm_tiles, it->d_files,
-                       it->d_pcm, reinterpret_cast<const unsigned *>(d_peak), force ? 1 : 0,
-                       reinterpret_cast<uint8_t *>(d_bytes));
-    LCFIR_HIP(hipGetLastError());
-    return LCFIR_OK;
+    return items_pass(it, s, lcfir::items_encode_scaled_kernel, it->n_pcm_tiles, it->d_out, it->d_pcm_tiles,
+                      it->n_pcm_tiles, it->d_files, it->pcm.d, reinterpret_cast<const unsigned *>(d_peak),
+                      force ? 1 : 0, reinterpret_cast<uint8_t *>(d_bytes));
 }
 
 int lcfir_items_encode_pcm_dither_dev(lcfir_items *it, const float *d_peak, int force, int dither, uint64_t seed,
@@ -2073,24 +2096,19 @@ int lcfir_items_encode_pcm_dither_dev(lcfir_items *it, const float *d_peak, int 
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int rc = items_pcm_table(it, byte_offset, format, s);
     if (rc) return rc;
-    items_note_stream(it, s);
     const auto kernel = dither == LCFIR_DITHER_TPDF ? lcfir::items_encode_dither_kernel<lcfir::kDitherTpdf>
                                                     : lcfir::items_encode_dither_kernel<lcfir::kDitherNone>;
-    hipLaunchKernelGGL(kernel, dim3(items_blocks(it->n_pcm_tiles)), dim3(lcfir::kItemThreads), 0, s, it->d_out,
-                       it->d_pcm_tiles, it->n_pcm_tiles, it->d_files, it->d_pcm,
-                       reinterpret_cast<const unsigned *>(d_peak), force ? 1 : 0, seed,
-                       reinterpret_cast<uint8_t *>(d_bytes));
-    LCFIR_HIP(hipGetLastError());
-    return LCFIR_OK;
+    return items_pass(it, s, kernel, it->n_pcm_tiles, it->d_out, it->d_pcm_tiles, it->n_pcm_tiles, it->d_files,
+                      it->pcm.d, reinterpret_cast<const unsigned *>(d_peak), force ? 1 : 0, seed,
+                      reinterpret_cast<uint8_t *>(d_bytes));
 }
 
 // The tensor calls' per-call table: check every live file's pointer and
-// stride, fill the next page-locked slot and queue its copy to d_span on s.
+// stride, fill the next page-locked slot and queue its copy to the span table on s.
 // The device table, the slots and their events are allocated here at the
 // first call, not in lcfir_items_create.
 static int items_span_table(lcfir_items *it, const float *const *ptr, const int64_t *stride, hipStream_t s) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs == hipStreamCaptureStatusActive)
+    if (stream_capturing(s))
         return fail(LCFIR_EINVAL, "the item set's gather and scatter calls cannot be captured into a HIP graph");
     const size_t arena_bytes = sizeof(float) * (size_t)it->arena;
     for (int32_t f = 0; f < it->nfiles; ++f) {
@@ -2109,31 +2127,16 @@ static int items_span_table(lcfir_items *it, const float *const *ptr, const int6
             return fail(LCFIR_EINVAL, "file %d: its memory overlaps the item set's arenas", f);
     }
     std::lock_guard<std::mutex> lk(it->mu);
-    const size_t tb = sizeof(lcfir::ItemSpan) * (size_t)it->nfiles;
-    if (!it->d_span && hipMalloc(reinterpret_cast<void **>(&it->d_span), tb) != hipSuccess) {
-        it->d_span = nullptr;
-        return fail(LCFIR_ENOMEM, "hipMalloc for the span table failed");
-    }
-    for (int k = 0; k < lcfir_items::kSpanSlots; ++k) {
-        if (!it->h_span[k] &&
-            hipHostMalloc(reinterpret_cast<void **>(&it->h_span[k]), tb, hipHostMallocDefault) != hipSuccess) {
-            it->h_span[k] = nullptr;
-            return fail(LCFIR_ENOMEM, "hipHostMalloc for the span table failed");
-        }
-        if (!it->span_done[k]) LCFIR_HIP(hipEventCreateWithFlags(&it->span_done[k], hipEventDisableTiming));
-    }
-    const int k = it->span_next;
-    if (it->span_pending[k]) LCFIR_HIP(hipEventSynchronize(it->span_done[k]));
-    it->span_pending[k] = false;
-    for (int32_t f = 0; f < it->nfiles; ++f) {
-        const bool live = it->group[(size_t)f] >= 0;
-        it->h_span[k][f] = lcfir::ItemSpan{live ? const_cast<float *>(ptr[f]) : nullptr, live ? stride[f] : 0};
-    }
-    LCFIR_HIP(hipMemcpyAsync(it->d_span, it->h_span[k], tb, hipMemcpyHostToDevice, s));
-    LCFIR_HIP(hipEventRecord(it->span_done[k], s));
-    it->span_pending[k] = true;
-    it->span_next = (k + 1) % lcfir_items::kSpanSlots;
-    return LCFIR_OK;
+    if (const int rc = it->span.ensure(it->nfiles)) return rc;
+    return it->span.push(
+        [&](lcfir::ItemSpan *slot) {
+            for (int32_t f = 0; f < it->nfiles; ++f) {
+                const bool live = it->group[(size_t)f] >= 0;
+                slot[f] = lcfir::ItemSpan{live ? const_cast<float *>(ptr[f]) : nullptr, live ? stride[f] : 0};
+            }
+            return (int)LCFIR_OK;
+        },
+        s);
 }
 
 int lcfir_items_gather_dev(lcfir_items *it, const float *const *d_src, const int64_t *src_stride, void *stream) {
@@ -2145,11 +2148,8 @@ int lcfir_items_gather_dev(lcfir_items *it, const float *const *d_src, const int
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int rc = items_span_table(it, d_src, src_stride, s);
     if (rc) return rc;
-    items_note_stream(it, s);
-    hipLaunchKernelGGL(lcfir::items_gather_kernel, dim3(items_blocks(it->n_row_tiles)), dim3(lcfir::kItemThreads),
-                       0, s, it->d_in, it->d_row_tiles, it->n_row_tiles, it->d_files, it->d_span);
-    LCFIR_HIP(hipGetLastError());
-    return LCFIR_OK;
+    return items_pass(it, s, lcfir::items_gather_kernel, it->n_row_tiles, it->d_in, it->d_row_tiles, it->n_row_tiles,
+                      it->d_files, it->span.d);
 }
 
 int lcfir_items_scatter_scaled_dev(lcfir_items *it, const float *d_peak, int force, float *const *d_dst,
@@ -2162,12 +2162,9 @@ int lcfir_items_scatter_scaled_dev(lcfir_items *it, const float *d_peak, int for
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int rc = items_span_table(it, d_dst, dst_stride, s);
     if (rc) return rc;
-    items_note_stream(it, s);
-    hipLaunchKernelGGL(lcfir::items_scatter_scaled_kernel, dim3(items_blocks(it->n_row_tiles)),
-                       dim3(lcfir::kItemThreads), 0, s, it->d_out, it->d_row_tiles, it->n_row_tiles, it->d_files,
-                       it->d_span, reinterpret_cast<const unsigned *>(d_peak), force ? 1 : 0);
-    LCFIR_HIP(hipGetLastError());
-    return LCFIR_OK;
+    return items_pass(it, s, lcfir::items_scatter_scaled_kernel, it->n_row_tiles, it->d_out, it->d_row_tiles,
+                      it->n_row_tiles, it->d_files, it->span.d, reinterpret_cast<const unsigned *>(d_peak),
+                      force ? 1 : 0);
 }
 
 int lcfir_dev_malloc(int device, size_t bytes, void **out) {
