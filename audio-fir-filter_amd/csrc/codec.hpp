@@ -11,8 +11,13 @@
 //   encode  float f -> clamp(rint(f * 2^(b-1)), -2^(b-1), 2^(b-1) - 1)  (RNE, in f64)
 //           float32    f -> f
 // Interleaved frames (WAV: little-endian, AIFF: big-endian) <-> planar
-// channels [nch][frames] with a channel stride.  Both kernels are HBM-bound
-// byte shuffles: one thread per interleaved sample, byte-exact, no MFMA.
+// channels [nch][frames] with a channel stride, byte-exact, no MFMA:
+//   decode_pcm_kernel         one thread per interleaved sample, byte loads;
+//   encode_pcm_dither_kernel  the one encode kernel behind lcfir_encode_pcm_dev,
+//                             _scaled_dev and _dither_dev: four samples a lane,
+//                             whole dwords stored where d_out allows, the
+//                             normalize (peak_scale.hpp's rule) folded in and
+//                             the dither a template parameter.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -67,55 +72,24 @@ __device__ __forceinline__ uint32_t encode_one(float v, const PcmFormat f) {
     return (uint32_t)(int32_t)(int64_t)q;
 }
 
-// grid-stride over interleaved sample index i = frame * nch + ch
+// Interleaved sample i = frame * nch + ch: its frame, and its channel in ch.
+__device__ __forceinline__ int64_t split_sample(int64_t i, int nch, int &ch) {
+    const int64_t fr = i / nch;
+    ch = (int)(i - fr * nch);
+    return fr;
+}
+
+// grid-stride over the interleaved sample index
 __global__ __launch_bounds__(256) void decode_pcm_kernel(const uint8_t *__restrict__ in, PcmFormat f,
                                                         int nch, int64_t frames,
                                                         float *__restrict__ out, int64_t stride) {
     const int64_t total = frames * nch;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
          i += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t fr = i / nch;
-        const int ch = (int)(i - fr * nch);
+        int ch;
+        const int64_t fr = split_sample(i, nch, ch);
         const uint32_t raw = load_bytes(in + i * f.bytes, f.bytes, f.big_endian);
         out[(int64_t)ch * stride + fr] = decode_one(raw, f);
-    }
-}
-
-__global__ __launch_bounds__(256) void encode_pcm_kernel(const float *__restrict__ in, int64_t stride,
-                                                        int nch, int64_t frames, PcmFormat f,
-                                                        uint8_t *__restrict__ out) {
-    const int64_t total = frames * nch;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-         i += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t fr = i / nch;
-        const int ch = (int)(i - fr * nch);
-        store_bytes(out + i * f.bytes, encode_one(in[(int64_t)ch * stride + fr], f), f.bytes,
-                    f.big_endian);
-    }
-}
-
-// encode_pcm_kernel with ProcessFile.cp:91-101's normalize folded in: the
-// per-file decision (peak = max d_peak[0..npeak); rescale iff peak > 1 or
-// force) is read from the device, and each sample is scaled exactly as
-// normalize_kernel does ((float)((double)v * (1.0 / (double)peak))) before
-// it is encoded -- byte-identical to normalize + encode, without the
-// rescale pass's 8 B/sample of HBM traffic.
-__global__ __launch_bounds__(256) void encode_pcm_scaled_kernel(const float *__restrict__ in, int64_t stride,
-                                                               int nch, int64_t frames, PcmFormat f,
-                                                               const unsigned *__restrict__ peak, int npeak,
-                                                               int force, uint8_t *__restrict__ out) {
-    float pk = 0.0f;
-    for (int i = 0; i < npeak; ++i) pk = fmaxf(pk, __uint_as_float(peak[i]));
-    const bool scale = (pk > 1.0f || force) && pk > 0.0f;
-    const double gain = scale ? 1.0 / (double)pk : 1.0;
-    const int64_t total = frames * nch;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-         i += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t fr = i / nch;
-        const int ch = (int)(i - fr * nch);
-        float v = in[(int64_t)ch * stride + fr];
-        if (scale) v = (float)((double)v * gain);
-        store_bytes(out + i * f.bytes, encode_one(v, f), f.bytes, f.big_endian);
     }
 }
 
@@ -241,13 +215,18 @@ __device__ __forceinline__ void store_quad(uint8_t *__restrict__ p, const uint32
     }
 }
 
-// encode_pcm_scaled_kernel with the dither option and whole-dword stores.
+// The encode, with ProcessFile.cp:91-101's normalize folded in: the per-file
+// decision (peak = max d_peak[0..npeak), rescale_rule) is read from the
+// device, and each sample is scaled exactly as normalize_kernel does before
+// it is encoded -- byte-identical to normalize + encode, without the rescale
+// pass's 8 B/sample of HBM traffic; npeak = 0 is the plain encode.
 // A lane produces four consecutive interleaved samples; where d_out is
 // 4-byte aligned every quad starts on a dword (4 * bytes per quad), so the
 // quads go out as dwords and only the buffer's last total % 4 samples as
-// bytes.  An unaligned d_out takes the sibling's byte store throughout.  The
+// bytes.  An unaligned d_out takes one byte store per sample throughout.  The
 // test is on a kernel argument, hence wave-uniform (items_gather_kernel's
-// float4 split).  Sample i of the call is frame frame0 + i / nch of its file.
+// float4 split).  Sample i of the call is frame frame0 + i / nch of its file
+// (kDitherNone uses neither seed nor frame0).
 template <int DITHER>
 __global__ __launch_bounds__(256) void encode_pcm_dither_kernel(const float *__restrict__ in, int64_t stride,
                                                                int nch, int64_t frames, PcmFormat f,
@@ -256,6 +235,7 @@ __global__ __launch_bounds__(256) void encode_pcm_dither_kernel(const float *__r
                                                                uint8_t *__restrict__ out) {
     float pk = 0.0f;
     for (int i = 0; i < npeak; ++i) pk = fmaxf(pk, __uint_as_float(peak[i]));
+    // rescale_rule (peak_scale.hpp) spelled out: through the helper the compiler turns two branches round
     const bool scale = (pk > 1.0f || force) && pk > 0.0f;
     const double gain = scale ? 1.0 / (double)pk : 1.0;
     const int64_t total = frames * nch;
@@ -281,8 +261,8 @@ __global__ __launch_bounds__(256) void encode_pcm_dither_kernel(const float *__r
         done = nquad * 4;
     }
     for (int64_t i = done + tid; i < total; i += nthreads) {
-        const int64_t fr = i / nch;
-        const int ch = (int)(i - fr * nch);
+        int ch;
+        const int64_t fr = split_sample(i, nch, ch);
         float v = in[(int64_t)ch * stride + fr];
         if (scale) v = (float)((double)v * gain);
         store_bytes(out + i * f.bytes, encode_one_dither<DITHER>(v, f, seed, ch, frame0 + (uint64_t)fr), f.bytes,

@@ -22,8 +22,8 @@
 // multiple of four floats into its row, so the row passes move float4s;
 // each thread has kItemLoads of them in flight (peak_scale.hpp's reasoning).
 // The sample rules themselves are codec.hpp's and peak_scale.hpp's
-// (decode_one, encode_one, scale_one, wave_max), so every value is the
-// per-file call's bit for bit.
+// (decode_one, encode_one_dither, split_sample, rescale_rule, scale_one,
+// wave_max), so every value is the per-file call's bit for bit.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -100,9 +100,9 @@ __global__ __launch_bounds__(kItemThreads) void items_normalize_kernel(float *__
                                                                        int force) {
     for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
         const ItemTile tl = tiles[t];
-        const float pk = __uint_as_float(peak[tl.file]);
-        if (!(pk > 1.0f || force) || !(pk > 0.0f)) continue;
-        const double gain = 1.0 / (double)pk;
+        const Rescale rs = rescale_rule(__uint_as_float(peak[tl.file]), force);
+        if (!rs.on) continue;
+        const double gain = rs.gain;
         float *__restrict__ p = y + tl.first;
         float4 *__restrict__ p4 = reinterpret_cast<float4 *>(p);
         const int n4 = tl.count >> 2;
@@ -210,9 +210,9 @@ __global__ __launch_bounds__(kItemThreads, 8) void items_scatter_scaled_kernel(c
                                                                             int force) {
     for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
         const ItemTile tl = tiles[t];
-        const float pk = peak ? __uint_as_float(peak[tl.file]) : 0.0f;
-        const bool scale = (pk > 1.0f || force) && pk > 0.0f;
-        const double gain = scale ? 1.0 / (double)pk : 1.0;
+        const Rescale rs = rescale_rule(peak ? __uint_as_float(peak[tl.file]) : 0.0f, force);
+        const bool scale = rs.on;
+        const double gain = rs.gain;
         const float *__restrict__ src = y + tl.first;
         float *__restrict__ dst = item_span_ptr(tl, files[tl.file], span[tl.file]);
         if ((reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
@@ -282,56 +282,18 @@ __global__ __launch_bounds__(kItemThreads) void items_decode_kernel(const uint8_
             const int k = (int)threadIdx.x + u * kItemThreads;
             if (k < tl.count) {
                 const int64_t i = tl.first + k;
-                const int64_t fr = i / fl.nch;
-                const int ch = (int)(i - fr * fl.nch);
+                int ch;
+                const int64_t fr = split_sample(i, fl.nch, ch);
                 dst[(int64_t)ch * fl.stride + fr] = decode_one(raw[u], io.f);
             }
         }
     }
 }
 
-// encode_pcm_scaled_kernel over every file at once: file f's decision comes
+// encode_pcm_dither_kernel over every file at once, the one kernel behind
+// lcfir_items_encode_pcm_scaled_dev and _dither_dev: file f's decision comes
 // from its own peak slot, each sample is scaled as items_normalize_kernel
-// would scale it and then encoded; the rows are left unscaled.
-__global__ __launch_bounds__(kItemThreads) void items_encode_scaled_kernel(const float *__restrict__ y,
-                                                                           const ItemTile *__restrict__ tiles,
-                                                                           int64_t ntiles,
-                                                                           const ItemFile *__restrict__ files,
-                                                                           const ItemPcm *__restrict__ pcm,
-                                                                           const unsigned *__restrict__ peak,
-                                                                           int force, uint8_t *__restrict__ out) {
-    for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
-        const ItemTile tl = tiles[t];
-        const ItemFile fl = files[tl.file];
-        const ItemPcm io = pcm[tl.file];
-        const float pk = __uint_as_float(peak[tl.file]);
-        const bool scale = (pk > 1.0f || force) && pk > 0.0f;
-        const double gain = scale ? 1.0 / (double)pk : 1.0;
-        const float *__restrict__ src = y + fl.off;
-        uint8_t *__restrict__ dst = out + io.byte_off;
-        float v[kItemPcmLoads];
-#pragma unroll
-        for (int u = 0; u < kItemPcmLoads; ++u) {
-            const int k = (int)threadIdx.x + u * kItemThreads;
-            if (k < tl.count) {
-                const int64_t i = tl.first + k;
-                const int64_t fr = i / fl.nch;
-                const int ch = (int)(i - fr * fl.nch);
-                v[u] = src[(int64_t)ch * fl.stride + fr];
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < kItemPcmLoads; ++u) {
-            const int k = (int)threadIdx.x + u * kItemThreads;
-            if (k < tl.count) {
-                const float s = scale ? scale_one(v[u], gain) : v[u];
-                store_bytes(dst + (tl.first + k) * io.f.bytes, encode_one(s, io.f), io.f.bytes, io.f.big_endian);
-            }
-        }
-    }
-}
-
-// encode_pcm_dither_kernel over every file at once.  ItemTile.first is the
+// would scale it and then encoded; the rows are left unscaled.  ItemTile.first is the
 // tile's first interleaved sample of its file, so with frame0 = 0 a sample's
 // noise is keyed on its own file's channel and frame: the bytes of a file are
 // the per-file call's whatever the batch.  Tiles start a multiple of
@@ -353,9 +315,9 @@ __global__ __launch_bounds__(kItemThreads) void items_encode_dither_kernel(const
         const ItemTile tl = tiles[t];
         const ItemFile fl = files[tl.file];
         const ItemPcm io = pcm[tl.file];
-        const float pk = peak ? __uint_as_float(peak[tl.file]) : 0.0f;
-        const bool scale = (pk > 1.0f || force) && pk > 0.0f;
-        const double gain = scale ? 1.0 / (double)pk : 1.0;
+        const Rescale rs = rescale_rule(peak ? __uint_as_float(peak[tl.file]) : 0.0f, force);
+        const bool scale = rs.on;
+        const double gain = rs.gain;
         const float *__restrict__ src = y + fl.off;
         uint8_t *__restrict__ dst = out + io.byte_off;
         int done = 0; // samples of the tile the dword path covers
@@ -387,8 +349,8 @@ __global__ __launch_bounds__(kItemThreads) void items_encode_dither_kernel(const
         }
         for (int k = done + (int)threadIdx.x; k < tl.count; k += kItemThreads) {
             const int64_t i = tl.first + k;
-            const int64_t fr = i / fl.nch;
-            const int ch = (int)(i - fr * fl.nch);
+            int ch;
+            const int64_t fr = split_sample(i, fl.nch, ch);
             const float v = src[(int64_t)ch * fl.stride + fr];
             const float s = scale ? scale_one(v, gain) : v;
             store_bytes(dst + i * io.f.bytes, encode_one_dither<DITHER>(s, io.f, seed, ch, (uint64_t)fr), io.f.bytes,

@@ -1511,39 +1511,6 @@ int lcfir_decode_pcm_dev(const void *d_in, int format, int32_t nch, int64_t fram
     return LCFIR_OK;
 }
 
-int lcfir_encode_pcm_dev(const float *d_in, int64_t in_stride, int32_t nch, int64_t frames,
-                         int format, void *d_out, void *stream) {
-    lcfir::PcmFormat f;
-    if (!pcm_format(format, f)) return fail(LCFIR_EINVAL, "unknown PCM format %d", format);
-    if (nch < 0 || frames < 0) return fail(LCFIR_EINVAL, "negative size");
-    if (nch == 0 || frames == 0) return LCFIR_OK;
-    if (!d_in || !d_out) return fail(LCFIR_EINVAL, "null argument");
-    if (nch > 1 && in_stride < frames) return fail(LCFIR_EINVAL, "channel stride < frames");
-    const int blocks = stream_blocks(frames * nch, 256 * 8);
-    hipLaunchKernelGGL(lcfir::encode_pcm_kernel, dim3(blocks), dim3(256), 0,
-                       reinterpret_cast<hipStream_t>(stream), d_in, in_stride, (int)nch, frames,
-                       f, reinterpret_cast<uint8_t *>(d_out));
-    LCFIR_HIP(hipGetLastError());
-    return LCFIR_OK;
-}
-
-int lcfir_encode_pcm_scaled_dev(const float *d_in, int64_t in_stride, int32_t nch, int64_t frames, int format,
-                                const float *d_peak, int32_t npeak, int force, void *d_out, void *stream) {
-    lcfir::PcmFormat f;
-    if (!pcm_format(format, f)) return fail(LCFIR_EINVAL, "unknown PCM format %d", format);
-    if (nch < 0 || frames < 0 || npeak < 0) return fail(LCFIR_EINVAL, "negative size");
-    if (nch == 0 || frames == 0) return LCFIR_OK;
-    if (!d_in || !d_out || (npeak > 0 && !d_peak)) return fail(LCFIR_EINVAL, "null argument");
-    if (nch > 1 && in_stride < frames) return fail(LCFIR_EINVAL, "channel stride < frames");
-    const int blocks = stream_blocks(frames * nch, 256 * 8);
-    hipLaunchKernelGGL(lcfir::encode_pcm_scaled_kernel, dim3(blocks), dim3(256), 0,
-                       reinterpret_cast<hipStream_t>(stream), d_in, in_stride, (int)nch, frames, f,
-                       reinterpret_cast<const unsigned *>(d_peak), (int)npeak, force ? 1 : 0,
-                       reinterpret_cast<uint8_t *>(d_out));
-    LCFIR_HIP(hipGetLastError());
-    return LCFIR_OK;
-}
-
 int lcfir_dither_tpdf(uint64_t seed, int32_t ch, int64_t frame0, int64_t count, double *d) {
     if (ch < 0) return fail(LCFIR_EINVAL, "negative channel %d", ch);
     if (frame0 < 0 || count < 0) return fail(LCFIR_EINVAL, "negative frame0 or count");
@@ -1559,9 +1526,11 @@ static int dither_mode(int dither) {
     return LCFIR_OK;
 }
 
-int lcfir_encode_pcm_dither_dev(const float *d_in, int64_t in_stride, int32_t nch, int64_t frames, int format,
-                                const float *d_peak, int32_t npeak, int force, int dither, uint64_t seed,
-                                int64_t frame0, void *d_out, void *stream) {
+// The per-file encode: every argument check and the one launch behind
+// lcfir_encode_pcm_dev, _scaled_dev and _dither_dev.
+static int encode_pcm(const float *d_in, int64_t in_stride, int32_t nch, int64_t frames, int format,
+                      const float *d_peak, int32_t npeak, int force, int dither, uint64_t seed, int64_t frame0,
+                      void *d_out, void *stream) {
     lcfir::PcmFormat f;
     if (!pcm_format(format, f)) return fail(LCFIR_EINVAL, "unknown PCM format %d", format);
     if (const int rc = dither_mode(dither)) return rc;
@@ -1580,6 +1549,23 @@ int lcfir_encode_pcm_dither_dev(const float *d_in, int64_t in_stride, int32_t nc
                        seed, (uint64_t)frame0, reinterpret_cast<uint8_t *>(d_out));
     LCFIR_HIP(hipGetLastError());
     return LCFIR_OK;
+}
+
+int lcfir_encode_pcm_dev(const float *d_in, int64_t in_stride, int32_t nch, int64_t frames,
+                         int format, void *d_out, void *stream) {
+    return encode_pcm(d_in, in_stride, nch, frames, format, nullptr, 0, 0, LCFIR_DITHER_NONE, 0, 0, d_out, stream);
+}
+
+int lcfir_encode_pcm_scaled_dev(const float *d_in, int64_t in_stride, int32_t nch, int64_t frames, int format,
+                                const float *d_peak, int32_t npeak, int force, void *d_out, void *stream) {
+    return encode_pcm(d_in, in_stride, nch, frames, format, d_peak, npeak, force, LCFIR_DITHER_NONE, 0, 0, d_out,
+                      stream);
+}
+
+int lcfir_encode_pcm_dither_dev(const float *d_in, int64_t in_stride, int32_t nch, int64_t frames, int format,
+                                const float *d_peak, int32_t npeak, int force, int dither, uint64_t seed,
+                                int64_t frame0, void *d_out, void *stream) {
+    return encode_pcm(d_in, in_stride, nch, frames, format, d_peak, npeak, force, dither, seed, frame0, d_out, stream);
 }
 
 // ---- item sets ---------------------------------------------------------------
@@ -2069,24 +2055,10 @@ int lcfir_items_decode_pcm_dev(lcfir_items *it, const void *d_bytes, const int64
                       it->d_pcm_tiles, it->n_pcm_tiles, it->d_files, it->pcm.d, it->d_in);
 }
 
-int lcfir_items_encode_pcm_scaled_dev(lcfir_items *it, const float *d_peak, int force, void *d_bytes,
-                                      const int64_t *byte_offset, const int32_t *format, void *stream) {
-    if (!it) return fail(LCFIR_EINVAL, "items is null");
-    if (it->n_pcm_tiles == 0) return LCFIR_OK;
-    if (!d_peak || !d_bytes || !byte_offset || !format) return fail(LCFIR_EINVAL, "null argument");
-    DeviceGuard g(it->device);
-    if (!g.ok) return fail(LCFIR_EDEVICE, "hipSetDevice(%d) failed", it->device);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const int rc = items_pcm_table(it, byte_offset, format, s);
-    if (rc) return rc;
-    return items_pass(it, s, lcfir::items_encode_scaled_kernel, it->n_pcm_tiles, it->d_out, it->d_pcm_tiles,
-                      it->n_pcm_tiles, it->d_files, it->pcm.d, reinterpret_cast<const unsigned *>(d_peak),
-                      force ? 1 : 0, reinterpret_cast<uint8_t *>(d_bytes));
-}
-
-int lcfir_items_encode_pcm_dither_dev(lcfir_items *it, const float *d_peak, int force, int dither, uint64_t seed,
-                                      void *d_bytes, const int64_t *byte_offset, const int32_t *format,
-                                      void *stream) {
+// The item set's encode: every argument check, the per-call table and the one
+// launch behind lcfir_items_encode_pcm_scaled_dev and _dither_dev.
+static int items_encode_pcm(lcfir_items *it, const float *d_peak, int force, int dither, uint64_t seed,
+                            void *d_bytes, const int64_t *byte_offset, const int32_t *format, void *stream) {
     if (!it) return fail(LCFIR_EINVAL, "items is null");
     if (const int rc = dither_mode(dither)) return rc;
     if (it->n_pcm_tiles == 0) return LCFIR_OK;
@@ -2101,6 +2073,19 @@ int lcfir_items_encode_pcm_dither_dev(lcfir_items *it, const float *d_peak, int 
     return items_pass(it, s, kernel, it->n_pcm_tiles, it->d_out, it->d_pcm_tiles, it->n_pcm_tiles, it->d_files,
                       it->pcm.d, reinterpret_cast<const unsigned *>(d_peak), force ? 1 : 0, seed,
                       reinterpret_cast<uint8_t *>(d_bytes));
+}
+
+int lcfir_items_encode_pcm_scaled_dev(lcfir_items *it, const float *d_peak, int force, void *d_bytes,
+                                      const int64_t *byte_offset, const int32_t *format, void *stream) {
+    // unlike the dither call, this one wants a peak wherever a file has rows
+    if (it && it->n_pcm_tiles > 0 && !d_peak) return fail(LCFIR_EINVAL, "null argument");
+    return items_encode_pcm(it, d_peak, force, LCFIR_DITHER_NONE, 0, d_bytes, byte_offset, format, stream);
+}
+
+int lcfir_items_encode_pcm_dither_dev(lcfir_items *it, const float *d_peak, int force, int dither, uint64_t seed,
+                                      void *d_bytes, const int64_t *byte_offset, const int32_t *format,
+                                      void *stream) {
+    return items_encode_pcm(it, d_peak, force, dither, seed, d_bytes, byte_offset, format, stream);
 }
 
 // The tensor calls' per-call table: check every live file's pointer and

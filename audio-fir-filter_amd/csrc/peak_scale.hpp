@@ -49,6 +49,21 @@ __device__ __forceinline__ float scale_one(float v, double gain) {
     return (float)((double)v * gain);
 }
 
+// The decision of ProcessFile.cp:98-101 for a peak and the normalize option:
+// rescale iff (peak > 1 or force) and peak > 0 (a silent file stays as it
+// is); the gain is 1 / peak in f64, and 1 where nothing is rescaled.  The
+// item passes take it from here; normalize_kernel and encode_pcm_dither_kernel
+// spell the same rule out (their instructions change through the helper).
+struct Rescale {
+    bool on;
+    double gain;
+};
+
+__device__ __forceinline__ Rescale rescale_rule(float pk, int force) {
+    const bool on = (pk > 1.0f || force) && pk > 0.0f;
+    return {on, on ? 1.0 / (double)pk : 1.0};
+}
+
 // Normalize: the decision is taken on the device from d_peak, so no host
 // round trip sits between the filter and the rescale.  Block (0, 0) also
 // zeroes clear[0, nclear) -- the next step's peak slots (a separate buffer),
@@ -61,6 +76,7 @@ __global__ __launch_bounds__(256) void normalize_kernel(float *__restrict__ y, i
         for (int i = threadIdx.x; i < nclear; i += blockDim.x) clear[i] = 0u;
     float pk = 0.0f;
     for (int i = 0; i < npeak; ++i) pk = fmaxf(pk, __uint_as_float(peak[i]));
+    // rescale_rule spelled out: through the helper the compiler turns the test and its branch round
     if (!(pk > 1.0f || force) || !(pk > 0.0f)) return;
     const double gain = 1.0 / (double)pk;
     float *__restrict__ p = y + (int64_t)blockIdx.y * stride;

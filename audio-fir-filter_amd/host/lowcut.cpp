@@ -376,16 +376,12 @@ void enqueue_file(Slot &s, Job &j, FilterSet &filters, PinnedPool &pool, const O
     check(lcfir_filter_channels_dev(flt.ctx, d_x, n, nch, n, d_y, n, d_peak, s.stream), "filter");
     // the normalize decision and gain ride in the encode pass, which reads every
     // sample anyway: no separate rescale pass over the f32 planes
-    if (o.dither)
-        // frame 0 of the file and the run's one seed: the same bytes wherever
-        // the file stands in the batch and whichever GPU it is dealt to
-        check(lcfir_encode_pcm_dither_dev(d_y, n, nch, n, f.pcm_format, d_peak, nch, o.normalize ? 1 : 0,
-                                          LCFIR_DITHER_TPDF, o.dither_seed, 0, d_raw, s.stream),
-              "encode");
-    else
-        check(lcfir_encode_pcm_scaled_dev(d_y, n, nch, n, f.pcm_format, d_peak, nch, o.normalize ? 1 : 0, d_raw,
-                                          s.stream),
-              "encode");
+    // with --dither: frame 0 of the file and the run's one seed, so the same
+    // bytes wherever the file stands in the batch and whichever GPU it is dealt to
+    check(lcfir_encode_pcm_dither_dev(d_y, n, nch, n, f.pcm_format, d_peak, nch, o.normalize ? 1 : 0,
+                                      o.dither ? LCFIR_DITHER_TPDF : LCFIR_DITHER_NONE, o.dither_seed, 0, d_raw,
+                                      s.stream),
+          "encode");
     check(lcfir_memcpy_d2h_async(f.data + f.data_offset, d_raw, f.data_bytes, s.stream), "d2h");
     check(lcfir_memcpy_d2h_async(s.peaks_host.get(), d_peak, sizeof(float) * (size_t)nch, s.stream),
           "d2h");

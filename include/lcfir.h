@@ -364,12 +364,16 @@ int lcfir_pcm_bytes(int format); /* bytes per sample, 0 for an unknown format */
 /* d_in: frames * nch interleaved samples; channel c goes to d_out + c*out_stride. */
 int lcfir_decode_pcm_dev(const void *d_in, int format, int32_t nch, int64_t frames,
                          float *d_out, int64_t out_stride, void *stream);
+/* Channel c is read from d_in + c*in_stride.  This is lcfir_encode_pcm_dither_dev
+ * (below) with LCFIR_DITHER_NONE, no peak (d_peak NULL, npeak 0, force 0), seed
+ * 0 and frame0 0: the same kernel, the same argument rules. */
 int lcfir_encode_pcm_dev(const float *d_in, int64_t in_stride, int32_t nch, int64_t frames,
                          int format, void *d_out, void *stream);
 /* lcfir_normalize_dev + lcfir_encode_pcm_dev in one pass (ProcessFile.cp:91-101
  * then :115-117): the normalize decision is taken from d_peak[0..npeak) on the
  * device and each sample is scaled exactly as lcfir_normalize_dev would scale
- * it before encoding -- byte-identical output, d_in is left unscaled. */
+ * it before encoding -- byte-identical output, d_in is left unscaled.  This is
+ * lcfir_encode_pcm_dither_dev with LCFIR_DITHER_NONE, seed 0 and frame0 0. */
 int lcfir_encode_pcm_scaled_dev(const float *d_in, int64_t in_stride, int32_t nch, int64_t frames,
                                 int format, const float *d_peak, int32_t npeak, int force,
                                 void *d_out, void *stream);
@@ -586,7 +590,10 @@ int lcfir_items_normalize_dev(lcfir_items *items, const float *d_peak, int force
  * byte_offset[f] in format[f] (lcfir_pcm_format); byte_offset and format are
  * host arrays of nfiles entries, copied before the call returns (entries of
  * files without rows are ignored).  These two calls cannot be captured into a
- * HIP graph (the per-call table is uploaded from the host). */
+ * HIP graph (the per-call table is uploaded from the host).
+ * lcfir_items_encode_pcm_scaled_dev is lcfir_items_encode_pcm_dither_dev
+ * (below) with LCFIR_DITHER_NONE and seed 0, except that it rejects a NULL
+ * d_peak where any file has rows. */
 int lcfir_items_decode_pcm_dev(lcfir_items *items, const void *d_bytes, const int64_t *byte_offset,
                                const int32_t *format, void *stream);
 int lcfir_items_encode_pcm_scaled_dev(lcfir_items *items, const float *d_peak, int force, void *d_bytes,

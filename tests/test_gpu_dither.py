@@ -1,8 +1,9 @@
-"""GPU tests of the dithered PCM encode (lcfir_encode_pcm_dither_dev,
-lcfir_items_encode_pcm_dither_dev, lowcut --dither) against the numpy
-restatement in dither_ref.py.  The noise is a pure function of (seed, channel,
-frame) and every step but one f64 add is exact, so bytes are compared with
-bytes: no tolerance anywhere."""
+"""GPU tests of the PCM encode through every entry point of its one kernel per
+layout (lcfir_encode_pcm_dev, _scaled_dev and _dither_dev;
+lcfir_items_encode_pcm_scaled_dev and _dither_dev; lowcut --dither) against the
+numpy restatement in dither_ref.py.  The noise is a pure function of (seed,
+channel, frame) and every step but one f64 add is exact, so bytes are compared
+with bytes: no tolerance anywhere."""
 import numpy as np
 import pytest
 
@@ -32,11 +33,14 @@ def src():
     return x
 
 
-def run_encode(lc, x, stride, fmt, dither, seed, frame0, out_off=0, peak=None, force=False, in_off=0):
+def run_encode(lc, x, stride, fmt, dither, seed, frame0, out_off=0, peak=None, force=False, in_off=0,
+               entry="dither"):
     """x: planar [nch][frames]; the call's input has `stride` floats between
     channels and starts in_off floats into its buffer, d_out starts out_off
-    bytes into a sentinel-filled one.  Returns the payload after checking that
-    the sentinel around it is intact."""
+    bytes into a sentinel-filled one.  entry: "dither" (lcfir_encode_pcm_dither_dev),
+    "scaled" (lcfir_encode_pcm_scaled_dev; no dither, frame0 unused) or "plain"
+    (lcfir_encode_pcm_dev; no peak either).  Returns the payload after checking
+    that the sentinel around it is intact."""
     nch, frames = x.shape
     nb = dr.NB[fmt[:3]] * nch * frames
     xin = np.full(in_off + nch * stride, np.float32(np.nan), np.float32)
@@ -45,8 +49,17 @@ def run_encode(lc, x, stride, fmt, dither, seed, frame0, out_off=0, peak=None, f
     d_x = lc.DeviceBuffer.from_array(xin)
     d_o = lc.DeviceBuffer.from_array(np.full(nb + 24, SENTINEL, np.uint8))
     d_pk = lc.DeviceBuffer.from_array(np.asarray(peak, np.float32)) if peak is not None else None
-    lc.encode_pcm_dither_dev(d_x.ptr + 4 * in_off, stride, nch, frames, fmt, d_pk, 0 if peak is None else len(peak),
-                             force, dither, seed, frame0, d_o.ptr + out_off)
+    d_in, d_out, npeak = d_x.ptr + 4 * in_off, d_o.ptr + out_off, 0 if peak is None else len(peak)
+    if entry == "dither":
+        lc.encode_pcm_dither_dev(d_in, stride, nch, frames, fmt, d_pk, npeak, force, dither, seed, frame0, d_out)
+    elif entry == "scaled":
+        assert dither == "none"
+        lc._check(lc.load().lcfir_encode_pcm_scaled_dev(d_in, stride, nch, frames, lc.PCM_FORMATS[fmt],
+                                                        d_pk.ptr if d_pk else None, npeak, 1 if force else 0,
+                                                        d_out, None))
+    else:
+        assert entry == "plain" and dither == "none" and peak is None and not force
+        lc.encode_pcm_dev(d_in, stride, nch, frames, fmt, d_out)
     lc.sync()
     got = d_o.download(nb + 24, np.uint8)
     assert np.all(got[:out_off] == SENTINEL) and np.all(got[out_off + nb:] == SENTINEL)
@@ -58,7 +71,8 @@ def run_encode(lc, x, stride, fmt, dither, seed, frame0, out_off=0, peak=None, f
 def test_grid(lc, src, fmt, dither):
     """Every format x channel count x length x d_out alignment, with an odd and
     an even input stride above the length (the even one lets one- and
-    two-channel rows load as float4 / float2)."""
+    two-channel rows load as float4 / float2).  Without dither the two older
+    entry points give the same bytes, each pinned on the helper's directly."""
     for nch in (1, 2, 3, 8):
         for frames in (1, 3, 4, 5, 257, 4099):
             x = src[:nch, :frames]
@@ -67,8 +81,9 @@ def test_grid(lc, src, fmt, dither):
                 for off in range(4):
                     if stride != frames + 3 and off not in (0, 3):
                         continue
-                    got = run_encode(lc, x, stride, fmt, dither, SEED, 0, out_off=off)
-                    assert got == want, (nch, frames, stride, off)
+                    for entry in ("dither", "scaled", "plain") if dither == "none" else ("dither",):
+                        got = run_encode(lc, x, stride, fmt, dither, SEED, 0, out_off=off, entry=entry)
+                        assert got == want, (nch, frames, stride, off, entry)
 
 
 @pytest.mark.parametrize("nch", [1, 2])
@@ -99,19 +114,6 @@ def test_split_invariance(lc, src, fmt):
     assert a + b == whole and whole == dr.encode_file(x, fmt, SEED)
 
 
-def scaled_dev(lc, x, fmt, peak, force):
-    nch, frames = x.shape
-    nb = dr.NB[fmt[:3]] * nch * frames
-    d_x = lc.DeviceBuffer.from_array(x)
-    d_o = lc.DeviceBuffer(nb)
-    d_pk = lc.DeviceBuffer.from_array(np.asarray(peak, np.float32)) if peak is not None else None
-    lc._check(lc.load().lcfir_encode_pcm_scaled_dev(d_x.ptr, frames, nch, frames, lc.PCM_FORMATS[fmt],
-                                                    d_pk.ptr if d_pk else None, 0 if peak is None else len(peak),
-                                                    1 if force else 0, d_o.ptr, None))
-    lc.sync()
-    return d_o.download(nb, np.uint8).tobytes()
-
-
 @pytest.mark.parametrize("fmt", FORMATS)
 def test_rescale_none_and_tpdf(lc, src, fmt):
     """With the normalize folded in: NONE is lcfir_encode_pcm_scaled_dev byte for
@@ -121,13 +123,14 @@ def test_rescale_none_and_tpdf(lc, src, fmt):
     for peak in (0.5, 1.0, 2.5):
         for force in (False, True):
             slots = [peak * 0.75, peak]
-            ref = scaled_dev(lc, x, fmt, slots, force)
+            ref = run_encode(lc, x, 4099, fmt, "none", SEED, 0, peak=slots, force=force, entry="scaled")
             assert run_encode(lc, x, 4099, fmt, "none", SEED, 0, peak=slots, force=force) == ref
             y = dr.rescale(x, peak, force)
             assert ref == dr.encode(y, fmt)
             assert run_encode(lc, x, 4099, fmt, "tpdf", SEED, 0, peak=slots, force=force) == \
                 dr.encode_file(y, fmt, SEED)
-    assert run_encode(lc, x, 4099, fmt, "none", SEED, 7) == scaled_dev(lc, x, fmt, None, True)
+    assert run_encode(lc, x, 4099, fmt, "none", SEED, 7) == \
+        run_encode(lc, x, 4099, fmt, "none", SEED, 0, force=True, entry="scaled")
     assert run_encode(lc, x, 4099, fmt, "tpdf", SEED, 0, force=True) == dr.encode_file(x, fmt, SEED)
 
 
@@ -179,7 +182,8 @@ ITEM_ALIGNS = [[1, 3, 0, 4, 2], [3, 1, 5, 7, 4]]
 @pytest.mark.parametrize("force,with_peak", [(False, True), (True, True), (False, False)])
 def test_items(lc, src, dither, aligns, force, with_peak):
     """Every file's bytes equal the per-file call's, whatever the batch; the
-    bytes between the payloads stay as they were."""
+    bytes between the payloads stay as they were.  With a peak and no dither
+    lcfir_items_encode_pcm_scaled_dev is held to the same helper bytes."""
     flt = lc.Filter(np.array([1.0]), device=0, method="direct")
     items = lc.ItemSet(flt, [n for _, n in ITEM_FILES], [c for c, _ in ITEM_FILES])
     files, offs, pos = [], [], 7
@@ -212,6 +216,16 @@ def test_items(lc, src, dither, aligns, force, with_peak):
         y = dr.rescale(x, peaks[f], force) if with_peak else x
         assert want == dr.encode_file(y, ITEM_FMTS[f], SEED, dither=dither == "tpdf"), f
     assert np.all(got[untouched] == SENTINEL)
+    if with_peak and dither == "none":
+        d_sc = lc.DeviceBuffer.from_array(np.full(pos, SENTINEL, np.uint8))
+        items.encode_pcm_scaled_dev(d_pk, force, d_sc, offs, ITEM_FMTS)
+        lc.sync()
+        got = d_sc.download(pos, np.uint8)
+        for f, x in enumerate(files):
+            if x.size:
+                want = dr.encode_file(dr.rescale(x, peaks[f], force), ITEM_FMTS[f], SEED, dither=False)
+                assert got[offs[f]:offs[f] + len(want)].tobytes() == want, f
+        assert np.all(got[untouched] == SENTINEL)
     if with_peak and dither == "tpdf" and not force:
         sc = lc.DeviceBuffer.from_array(np.full(pos, SENTINEL, np.uint8))
         items.encode_pcm_dither_dev(d_pk, force, "none", SEED, sc, offs, ITEM_FMTS)
