@@ -1,6 +1,6 @@
 """Known-answer taps and tap families (test infrastructure: inputs and exact
-expected outputs for tests/test_known_answer_ref.py and
-tests/test_gpu_tap_domain.py).
+expected outputs for tests/test_known_answer_ref.py,
+tests/test_gpu_tap_domain.py and tests/test_gpu_plan_limits.py).
 
 The filtered sample (include/lcfir.h): y[n] = sum_k h[k] x[n - half + k], half =
 (T - 1) / 2, x = 0 outside [0, N).  Sparse taps make that sum one or two

@@ -1,5 +1,7 @@
 """The known-answer helpers (tests/known_answer.py) against the oracle, on the
-CPU: what tests/test_gpu_tap_domain.py expects of the kernels is what the
+CPU: what tests/test_gpu_tap_domain.py and tests/test_gpu_plan_limits.py (the
+shortest, the longest one-partition, the first two-partition and the longest
+filters of the FFT method) expect of the kernels is what the
 long-double oracle computes bit for bit, and what an f64 FFT convolution
 narrows to; the threshold taps sit on the side of 2^-50 they claim; the
 partition edges are fft_partition_taps' (fir_fft.hpp)."""
@@ -9,7 +11,12 @@ import pytest
 import known_answer as ka
 
 N = 20_001
-TAPS = [15, 801, 4001, 4003]
+# 1, 3, 5: the shortest filters of tests/test_gpu_plan_limits.py (half 0, 1, 2)
+TAPS = [1, 3, 5, 15, 801, 4001, 4003]
+# its long tap counts, with the partitions they run in (fft_partition_count at L = 16 384 / 32 768):
+# checked at sampled outputs
+LIMIT_TAPS = [(10_921, 1), (10_923, 1), (10_925, 2), (21_845, 1), (21_847, 1), (21_849, 2)]
+T_MAX = 1_048_575  # the FFT method's longest filter: 127 partitions at L = 16 384, 64 at 32 768
 
 
 @pytest.fixture(scope="module")
@@ -79,6 +86,71 @@ def test_f64_fft_convolution_narrows_to_expected_bits(x, T):
     assert worst <= 9.1e-13 / 100, f"T={T}: f64 FFT max error {worst:.3e} against the 9.1e-13 half-spacing"
 
 
+def _limit_cases(T, parts):
+    """The delays and pairs test_gpu_plan_limits.py runs at T taps in `parts` partitions."""
+    ks = ka.delay_ks(T, ka.partition_edges(T, ka.partition_taps(T, parts), parts))
+    return [(f"delay k={k}", ka.delay_taps(T, k), lambda x, k=k: ka.expect_delay(x, T, k)) for k in ks] + \
+           [(f"pair d={d}", ka.pair_taps(T, d), lambda x, d=d: ka.expect_pair(x, T, d)) for d in ka.pair_ds(T)]
+
+
+def _sampled(n, half, count, seed):
+    """Both ends, either side of the first and last full-length sum, random positions."""
+    idx = np.r_[np.arange(8), np.arange(n - 8, n), half + np.arange(-2, 3), n - 1 - half + np.arange(-2, 3),
+                np.random.default_rng(seed).integers(0, n, count)]
+    return np.unique(idx[(idx >= 0) & (idx < n)])
+
+
+@pytest.mark.parametrize("T,parts", LIMIT_TAPS)
+def test_oracle_reproduces_expected_bits_at_the_plan_limits(oracle_mod, T, parts):
+    """The long tap counts of test_gpu_plan_limits.py, at ~550 sampled outputs of a 60 001-sample channel."""
+    n = 60_001
+    x = ka.grid16(np.random.default_rng(T), 1, n)[0]
+    idx = _sampled(n, (T - 1) // 2, 512, T)
+    cases = _limit_cases(T, parts)
+    # 7 delays (two partitions meet at the centre tap: their edges are half and half + 1) and 4 pairs
+    assert len(cases) == 11 and (parts == 1 or ka.partition_taps(T, 2) == (T - 1) // 2 + 1)
+    for name, taps, expect in cases:
+        want = expect(x)
+        got, _ = oracle_mod.filter_points(x, taps, idx, oracle_mod.MODE_LD)
+        assert np.array_equal(got.view(np.int32), want[idx].view(np.int32)), (T, name)
+        assert np.count_nonzero(want) > n // 4 and np.count_nonzero(want[idx]) > idx.size // 4, (T, name)
+
+
+@pytest.mark.parametrize("T,parts", LIMIT_TAPS)
+def test_f64_fft_convolution_narrows_at_the_plan_limits(T, parts):
+    """test_f64_fft_convolution_narrows_to_expected_bits at the long tap counts, every output."""
+    n = 60_001
+    x = ka.grid16(np.random.default_rng(T), 1, n)[0]
+    half = (T - 1) // 2
+    nfft = 1 << 17
+    assert nfft >= n + T
+    X = np.fft.rfft(x.astype(np.float64), nfft)
+    worst = 0.0
+    for name, taps, expect in _limit_cases(T, parts):
+        want = expect(x)
+        y64 = np.fft.irfft(X * np.fft.rfft(taps[::-1], nfft), nfft)[half:half + n]
+        worst = max(worst, float(np.abs(y64 - want.astype(np.float64)).max()))
+        ka.assert_known(y64.astype(np.float32), want, exact_zero=False, where=f"T={T} {name}")
+    assert worst <= 9.1e-13 / 100, f"T={T}: f64 FFT max error {worst:.3e} against the 9.1e-13 half-spacing"
+
+
+@pytest.mark.parametrize("tp", [8257, 16385])
+def test_oracle_reproduces_expected_bits_of_the_longest_filter(oracle_mod, tp):
+    """1 048 575 taps: the three delays test_gpu_plan_limits.py runs per segment
+    length (k = 0, T - 1 and 63 tp), at ~150 sampled outputs of a channel of
+    the length that test uses."""
+    T = T_MAX
+    half = (T - 1) // 2
+    n = T + ((16384 if tp == 8257 else 32768) - tp + 1) // 2  # T + B // 2
+    x = ka.grid16(np.random.default_rng(n), 1, n)[0]
+    idx = _sampled(n, half, 128, tp)
+    for k in (0, T - 1, 63 * tp):
+        want = ka.expect_delay(x, T, k)
+        got, _ = oracle_mod.filter_points(x, ka.delay_taps(T, k), idx, oracle_mod.MODE_LD)
+        assert np.array_equal(got.view(np.int32), want[idx].view(np.int32)), (T, k)
+        assert np.count_nonzero(want) > n // 4 and np.count_nonzero(want[idx]) > idx.size // 4, (T, k)
+
+
 def test_assert_known_sees_one_wrong_output():
     x = ka.grid16(np.random.default_rng(3), 2, 1000)
     want = ka.expect_delay(x, 15, 0)  # y[n] = x[n - 7]: the first 7 outputs of each channel are 0
@@ -130,7 +202,15 @@ def test_threshold_taps_sit_on_the_requested_side(oracle_mod, T):
 
 @pytest.mark.parametrize("T,parts,tp,edges", [
     (40_001, 5, 8001, [0, 8000, 8001, 16001, 16002, 24002, 24003, 32003, 32004, 40_000]),
-    (100_001, 6, 16667, [0, 16666, 16667, 33333, 33334, 50000, 50001, 66667, 66668, 83334, 83335, 100_000])])
+    (100_001, 6, 16667, [0, 16666, 16667, 33333, 33334, 50000, 50001, 66667, 66668, 83334, 83335, 100_000]),
+    # tests/test_gpu_plan_limits.py: the first two-partition plan of either segment length ...
+    (10_925, 2, 5463, [0, 5462, 5463, 10_924]),
+    (21_849, 2, 10_925, [0, 10_924, 10_925, 21_848]),
+    # ... and the longest filter at either segment length (64 / 65 zero taps behind the last partition)
+    (1_048_575, 127, 8257, sorted({0, 1_048_574} | {8257 * p - 1 for p in range(1, 127)} |
+                                  {8257 * p for p in range(1, 127)})),
+    (1_048_575, 64, 16_385, sorted({0, 1_048_574} | {16_385 * p - 1 for p in range(1, 64)} |
+                                   {16_385 * p for p in range(1, 64)}))])
 def test_partition_edges_restated(T, parts, tp, edges):
     """fft_partition_taps = ceil(T / parts) | 1, written out for both
     partitioned forms; the last partition is the short one."""
